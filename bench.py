@@ -2,6 +2,7 @@
 """Headline benchmark: edges aggregated / sec on TrackML-1GeV-shaped graphs, latent=256.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling both|weak|strong] [--event headline|full_pileup]
+                    [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the aggregation hot path over one event: the K1
 ``scatter_add(edges[M,256], graph[1], dim_size=N)`` of the message-passing cell
@@ -26,14 +27,23 @@ next aggregation depends on the edge update, which depends on the halo: gnn_util
 the exchange and the bench does not pretend it can; the model path overlaps it with the interior-edge MLP
 (partition.distributed_cell_forward), which this K1-only step does not contain.
 
-One line carries BOTH scaling figures (``--scaling both``, the default):
+Scaling figures (``--scaling both``, the default):
   value / scaling "weak"   the event grows with P (P x 120k hits / P x 1M edges, per-GPU work fixed); N = 1 is
                            the BENCH line;
   "strong_scaling": {...}   ONE fixed event for every P: the full-pileup event of BASELINE config 5 (480k hits,
-                           4M edges -> 8M rows), with per-rank rows / halo bytes / imbalance.
+                           4M edges -> 8M rows), with per-rank rows / halo bytes / imbalance (``--full`` only).
 ``--scaling weak|strong`` runs one of them only (``strong`` then fills ``value``).
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` and `cpu_baseline` objects.
+A plain run measures only the headline figure: set-up, warm-up, the K timed steps, and the result line (with the
+`roofline` derived from those steps' events).  ``--full`` adds what takes runs of its own: the strong-scaling mode
+of ``--scaling both``, the destination-sorted layout, the plan build time and the CPU baseline.
+
+``--dump-outputs DIR`` writes, after the timed steps, the K1 result of the last timed step as float32 ``.npy``
+files: a fixed, seeded sample of at most 32 MiB of its rows (``k1_out.npy``) and the sampled row numbers
+(``k1_out_rows.npy``, float64); rank r > 0 of a multi-GPU run adds ``_rank{r}`` to both names.  Inputs are seeded,
+so two builds given the same arguments can be compared file for file.
+
+Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` and (``--full``) `cpu_baseline` objects.
 """
 from __future__ import annotations
 
@@ -70,7 +80,12 @@ def parse(argv=None):
     ap.add_argument("--scaling", default="both", choices=["both", "weak", "strong"])
     ap.add_argument("--event", default=None, choices=sorted(EVENTS),
                     help="default: headline for weak scaling, full_pileup for strong scaling")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures: strong scaling (with --scaling both), the sorted layout, "
+                         "the plan build time and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write a seeded sample of the last timed step's K1 output to DIR as .npy files")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--halo-mode", default="auto", choices=["auto", "all_gather", "all_to_all"],
                     help="auto: both are timed during warm-up and the faster one (max over ranks) is used")
     ap.add_argument("--selftest-launch", action="store_true",
@@ -78,7 +93,10 @@ def parse(argv=None):
                          "exchange on CPU tensors and print the sharding statistics; measures nothing")
     ap.add_argument("--sizes", type=int, nargs=2, default=None, metavar=("HITS", "EDGES"),
                     help="per-GPU (weak) / total (strong) event size override (rehearsals and tests)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def event_size(scaling: str, event: str | None, world: int):
@@ -244,8 +262,24 @@ def _all_max(dist, value: float, device) -> float:
     return float(t[0])
 
 
-def measure(args, scaling: str, world: int, rank: int, device, dist, coll_device, with_sorted: bool):
-    """run one scaling mode; returns the result dict (meaningful on rank 0)"""
+def dump_outputs(out_dir: str, out: torch.Tensor, rank: int, world: int, budget_bytes: int = 32 << 20):
+    """a fixed, seeded sample of the rows of `out` (the same rows for every build) -> out_dir/k1_out*.npy, float32;
+    the sampled row numbers go alongside as float64 (exact below 2**53)"""
+    import numpy as np
+    n, width = out.shape
+    k = min(n, max(1, budget_bytes // world // (4 * max(width, 1))))
+    rows = torch.randperm(n, generator=torch.Generator().manual_seed(4321))[:k].sort().values
+    sample = out.index_select(0, rows.to(out.device)).float().cpu().numpy()
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"k1_out{suffix}.npy"), np.ascontiguousarray(sample, np.float32))
+    np.save(os.path.join(out_dir, f"k1_out_rows{suffix}.npy"), rows.numpy().astype(np.float64))
+
+
+def measure(args, scaling: str, world: int, rank: int, device, dist, coll_device, with_sorted: bool,
+            dump: bool = False):
+    """run one scaling mode; returns the result dict (meaningful on rank 0).  `dump`: write the last timed step's
+    output to args.dump_outputs"""
     import hierarchicalgnn_amd as H
     L = args.latent
     t_setup = time.perf_counter()
@@ -256,15 +290,17 @@ def measure(args, scaling: str, world: int, rank: int, device, dist, coll_device
     plan = H.get_plan(graph[1], n_local)          # first build also loads the code object
     torch.cuda.synchronize()
     setup_s = time.perf_counter() - t_setup
-    builds = []
-    for _ in range(3):                             # warm per-event cost: sort + CSR + work list, host wall, synced
-        idx_copy = graph[1].clone()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        H.GraphPlan(idx_copy, n_local)
-        torch.cuda.synchronize()
-        builds.append((time.perf_counter() - t0) * 1e3)
-    plan_ms = sorted(builds)[1]
+    plan_ms = None
+    if args.full:
+        builds = []
+        for _ in range(3):                         # warm per-event cost: sort + CSR + work list, host wall, synced
+            idx_copy = graph[1].clone()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            H.GraphPlan(idx_copy, n_local)
+            torch.cuda.synchronize()
+            builds.append((time.perf_counter() - t0) * 1e3)
+        plan_ms = sorted(builds)[1]
 
     def barrier():
         if dist is not None:
@@ -311,11 +347,14 @@ def measure(args, scaling: str, world: int, rank: int, device, dist, coll_device
     ends = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(starts[i], ends[i])
+        out = step(starts[i], ends[i])
     barrier()
     elapsed = time.perf_counter() - t0
     ev_ms = sorted(s.elapsed_time(e) for s, e in zip(starts, ends))
     kern_ms = sum(ev_ms) / len(ev_ms)
+    if dump:
+        dump_outputs(args.dump_outputs, out, rank, world)
+    del out
 
     stats = torch.tensor([elapsed, float(M)], dtype=torch.float64, device=coll_device)
     if dist is not None:
@@ -469,11 +508,16 @@ def run_rank(args):
             if args.halo_mode == "auto":
                 args.halo_mode = "all_gather"       # gloo has no device all_to_all
 
-    modes = ["weak", "strong"] if args.scaling == "both" else [args.scaling]
+    if args.scaling == "both":
+        modes = ["weak", "strong"] if args.full else ["weak"]
+    else:
+        modes = [args.scaling]
     results = {}
     for m in modes:
-        # at N = 1 weak == the BENCH line; the sorted-layout figure rides on the first mode only
-        results[m] = measure(args, m, world, rank, device, dist, coll_device, with_sorted=(world == 1 and m == modes[0]))
+        # at N = 1 weak == the BENCH line; the sorted-layout figure (--full) rides on the first mode only
+        results[m] = measure(args, m, world, rank, device, dist, coll_device,
+                             with_sorted=(args.full and world == 1 and m == modes[0]),
+                             dump=(args.dump_outputs is not None and m == modes[0]))
 
     if rank == 0:
         main_mode = modes[0]
@@ -514,7 +558,7 @@ def run_rank(args):
                                      "setup_s")},
                 "roofline": s["roofline"],
             }
-        if world == 1 and not args.no_cpu_baseline and r["_dst_cpu"] is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and r["_dst_cpu"] is not None:
             res["cpu_baseline"] = cpu_baseline(r["_dst_cpu"], r["_n_hits"], args.latent)
         else:
             res["cpu_baseline"] = None
