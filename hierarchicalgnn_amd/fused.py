@@ -3,7 +3,7 @@
 (csrc/mlp_fused_bf16.hip, bf16 rows).  Covers the cell networks, the encoders (small-K mode)
 and the width-1 classifier heads.
 
-``supported`` decides per call; when it says no, ``concat_mlp`` evaluates the same
+``_route`` decides per call (``supported`` asks it); when it says no, ``concat_mlp`` evaluates the same
 Sequential with HIP row gathers + library GEMMs (still on the GPU).  The fused kernel is
 used whenever autograd is not recording: inference, and the first (no-grad) pass of every
 reentrant ``torch.utils.checkpoint`` segment -- which is how the reference runs all of its
@@ -19,7 +19,7 @@ import contextvars
 import ctypes
 import os
 import weakref
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -44,7 +44,7 @@ stats = {"fused_calls": 0, "fused_train_calls": 0}
 _ctx_options = contextvars.ContextVar("hgnn_fused_options", default=None)
 _ctx_training_forward = contextvars.ContextVar("hgnn_fused_training_forward", default=0)
 _OPTION_NAMES = ("enabled", "train_enabled", "preproject", "preproject_bf16", "fp32_split3", "fp32_split3_train",
-                 "bf16_split", "train_bf16_enabled", "wgrad_hip", "bwd_fused")
+                 "bf16_split", "train_bf16_enabled")
 
 
 def _opt(name: str):
@@ -57,11 +57,11 @@ def _opt(name: str):
 @contextlib.contextmanager
 def options(**overrides):
     """Context-local dispatch overrides: ``enabled``, ``train_enabled``, ``preproject``, ``preproject_bf16``,
-    ``fp32_split3``, ``fp32_split3_train``, ``bf16_split``, ``train_bf16_enabled``, ``wgrad_hip``, ``bwd_fused``.
+    ``fp32_split3``, ``fp32_split3_train``, ``bf16_split``, ``train_bf16_enabled``.
     Nested contexts stack; nothing outside the ``with`` block (or in another thread) sees the change.
     NOTE for training: autograd runs the backward (and the recompute of reentrant checkpoints) on its own worker
     thread, which does NOT inherit this context -- switches that must hold during ``backward()`` (``fp32_split3_train``,
-    ``train_enabled``, ``train_bf16_enabled``, ``wgrad_hip``, ``bwd_fused``) are to be set as process defaults
+    ``train_enabled``, ``train_bf16_enabled``) are to be set as process defaults
     (``set_*`` functions / HGNN_* environment variables); ``options`` is for inference-side choices."""
     bad = set(overrides) - set(_OPTION_NAMES)
     if bad:
@@ -146,32 +146,45 @@ def _pad_rows(t: torch.Tensor, rows: int) -> torch.Tensor:
     return out
 
 
-def _descriptor(net, segments, skip, dry=False, split_proj=False):
-    """(descriptor, keep-alive list, M, n_out) for hgnn_mlp_forward_f32, or None.  ``dry``: only decide
-    supportability (no projection GEMMs are run; the descriptor must not be launched).  ``split_proj``: the caller will
-    run the split-bf16 kernel on this descriptor: the N-row projection GEMMs of the gathered segments use the same
-    arithmetic (hgnn_linear_f32_split3, four products) instead of the library's fp32 GEMM."""
-    layers = _parse(net)
-    if layers is None or len(layers) not in (1, 2, 3) or not (1 <= len(segments) <= 3):
+def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = False, dry: bool = False, layers=None):
+    """(descriptor, keep-alive list, M, n_out) for ``hgnn_mlp_forward_<entry>`` (``entry`` in f32, f32_split3, bf16,
+    bf16_split), or None.  ``layers``: ``_parse(net)`` when the caller has it (then ``net`` is not read).
+
+    One walk for every kernel: the segments (one row count M, int32 gather indices, pre-projected segments
+    ``hgnn_mlp_desc.n_pre`` vs the ones kept in the kernel's K loop), the layers (chained widths, one LayerNorm eps)
+    and the skip rows.  What depends on the kernel: the row dtype, which segments are pre-projected (fp32: by
+    ``_projected_segments``; bf16: only for the split kernel, by ``preproject_bf16``, P rounded once to bf16) and the
+    weight layout of each layer (below).  ``dry``: only decide supportability (no projection GEMM or weight
+    preparation runs; the descriptor must not be launched).  ``split_proj`` (f32_split3): the N-row projection GEMMs
+    use the consuming kernel's arithmetic (hgnn_project_f32_split3, three products) instead of the library's fp32 GEMM."""
+    bf16 = entry.startswith("bf16")
+    split = entry == "bf16_split"
+    dt = torch.bfloat16 if bf16 else torch.float32
+    layers = _parse(net) if layers is None else layers
+    if layers is None or not (1 <= len(layers) <= 3 and 1 <= len(segments) <= 3):
         return None
-    if any(ln is None for _, ln, _ in layers[:-1]):
+    if any(ln is None for _, ln, _ in (layers if bf16 else layers[:-1])):
         return None
     d = _lib.HgnnMlpDesc()
     keep = []
     M = None
     for table, index in segments:
-        if table.dim() != 2 or not table.is_cuda or table.dtype != torch.float32:
+        if table.dim() != 2 or not table.is_cuda or table.dtype != dt:
             return None
         rows = int(index.numel()) if index is not None else int(table.shape[0])
         if M is None:
             M = rows
         elif M != rows:
             return None
-    K_full = sum(int(t.shape[1]) for t, _ in segments)
     lin0 = layers[0][0]
-    if lin0.in_features != K_full:
+    if lin0.in_features != sum(int(t.shape[1]) for t, _ in segments) or not lin0.weight.is_cuda:
         return None
-    proj = _projected_segments(segments, M) if layers[0][1] is not None else []
+    if bf16:
+        pre = _opt("preproject_bf16")
+        pre = split and (len(layers) > 1 and lin0.out_features >= 512 if pre is None else pre)
+    else:
+        pre = layers[0][1] is not None
+    proj = _projected_segments(segments, M) if pre else []
     split_P = {}
     if split_proj and proj and not dry:
         # the pre-projections in the consuming kernel's own arithmetic; both segments of one table (nodes[graph[0]],
@@ -188,9 +201,8 @@ def _descriptor(net, segments, skip, dry=False, split_proj=False):
             res = _split3_project(segments[grp[0]][0].detach(), lin0.weight, [cols[i] for i in grp])
             if res is not None:
                 split_P.update(dict(zip(grp, res)))
-    col = 0
+    col = n_kept = n_pre = 0
     kept_cols = []
-    n_kept = n_pre = 0
     for i, (table, index) in enumerate(segments):
         t = table if table.is_contiguous() else table.contiguous()
         keep.append(t)
@@ -205,8 +217,11 @@ def _descriptor(net, segments, skip, dry=False, split_proj=False):
             else:
                 P = split_P.get(i)
                 if P is None:
-                    with torch.autocast("cuda", enabled=False):   # the kernel reads P as fp32
-                        P = torch.matmul(t.detach(), lin0.weight.detach()[:, col:col + w].t())   # [rows, H]
+                    W_s = lin0.weight.detach()[:, col:col + w]
+                    with torch.autocast("cuda", enabled=False):
+                        # the kernel reads P in its row dtype; bf16: bf16 operands, fp32 accumulation, one rounding --
+                        # the arithmetic the kernel's own MFMAs would do
+                        P = torch.matmul(t.detach(), (W_s.to(torch.bfloat16) if bf16 else W_s).t())   # [rows, H]
                 keep.append(P)
             d.pre_table[n_pre] = P.data_ptr()
             d.pre_index[n_pre] = i32.data_ptr() if i32.numel() else None
@@ -227,57 +242,72 @@ def _descriptor(net, segments, skip, dry=False, split_proj=False):
     for l, (lin, ln, act) in enumerate(layers):
         if l > 0 and lin.in_features != d.width[l]:
             return None
-        params = [lin.weight, lin.bias] + ([ln.weight, ln.bias] if ln is not None else [])
-        for p in params:
-            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                return None
-        W, b = lin.weight, lin.bias
-        if l == 0 and n_pre:
-            # the kernel's K loop only sees the columns of the segments that stayed
-            W = W.detach() if dry else torch.cat([W.detach()[:, c0:c1] for c0, c1 in kept_cols], dim=1).contiguous()
-            keep.append(W)
-        if l == 0 and any(int(t.shape[1]) % 16 for t, _ in segments):
-            if K > 16:
-                return None
-            # small-K mode (encoders, K = 3 / 6): one zero-padded 16-column chunk
-            W = torch.nn.functional.pad(W.detach(), (0, 16 - K)).contiguous()
-            keep.append(W)
-            d.w0_cols = 16
-        lnw_t, lnb_t = (ln.weight, ln.bias) if ln is not None else (None, None)
+        cols = tuple(kept_cols) if (l == 0 and n_pre) else None    # the kernel's K loop only sees the kept segments
+        W, b = lin.weight.detach(), lin.bias.detach()
+        lnw, lnb = (ln.weight.detach(), ln.bias.detach()) if ln is not None else (None, None)
         o_l = int(lin.out_features)
-        if l == n - 1 and ln is None:
-            if o_l > 32:
+        if bf16:
+            # bf16 copies of the weights: A-fragment order (split kernel) or k-slot column order (W_{l>=1}); bias and
+            # LayerNorm parameters in fp32
+            if not W.is_cuda:
                 return None
-            # head (width-1 classifiers, emb_dim-wide embedding head): the plain last layer is stored
-            # zero-padded as 32 rows
-            W, b = _pad_rows(W.detach(), 32), _pad_rows(b.detach(), 32)
-            keep += [W, b]
-            d.w_last_rows = 32
-        elif l == n - 1 and n == 3 and o_l not in (32, 64, 128, 256) and layers[0][0].out_features % 2 == 0:
-            # narrower than its tile row (supernode encoder, L - emb_dim outputs): Linear / LayerNorm
-            # parameters zero-padded to P = hidden / 2 rows; the kernel normalises over the real width
-            P = layers[0][0].out_features // 2
-            if not (P - 16 < o_l < P) or o_l % 4:
+            if split:
+                if (K if cols else lin.in_features) % 32 or o_l % 64:
+                    return None
+                if not dry:
+                    W = _prepared_weight(lin.weight, cols)
+            else:
+                if l > 0 and lin.in_features % 32:
+                    return None
+                if not dry:
+                    W = (W[:, _kslot_perm(lin.in_features, W.device)] if l > 0 else W).to(torch.bfloat16).contiguous()
+            b, lnw, lnb = (p.float().contiguous() for p in (b, lnw, lnb))
+        else:
+            # fp32 weights as they are (f32_split3: their bf16 split stream), padded where the kernel wants more
+            if any(not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous()
+                   for p in (W, b) + ((lnw, lnb) if ln is not None else ())):
                 return None
-            W, b = _pad_rows(W.detach(), P), _pad_rows(b.detach(), P)
-            lnw_t, lnb_t = _pad_rows(ln.weight.detach(), P), _pad_rows(ln.bias.detach(), P)
-            keep += [W, b, lnw_t, lnb_t]
-            d.w_last_rows = P
+            if entry == "f32_split3" and not dry:
+                W = _split3_weight(lin.weight, cols, l == 0)
+            elif cols and not dry:
+                W = torch.cat([W[:, c0:c1] for c0, c1 in cols], dim=1).contiguous()
+            if l == 0 and any(int(t.shape[1]) % 16 for t, _ in segments):
+                if K > 16:
+                    return None
+                # small-K mode (encoders, K = 3 / 6): one zero-padded 16-column chunk
+                W = torch.nn.functional.pad(W, (0, 16 - K)).contiguous()
+                d.w0_cols = 16
+            if l == n - 1 and ln is None:
+                if o_l > 32:
+                    return None
+                # head (width-1 classifiers, emb_dim-wide embedding head): the plain last layer is stored
+                # zero-padded as 32 rows
+                W, b = _pad_rows(W, 32), _pad_rows(b, 32)
+                d.w_last_rows = 32
+            elif l == n - 1 and n == 3 and o_l not in (32, 64, 128, 256) and layers[0][0].out_features % 2 == 0:
+                # narrower than its tile row (supernode encoder, L - emb_dim outputs): Linear / LayerNorm
+                # parameters zero-padded to P = hidden / 2 rows; the kernel normalises over the real width
+                P = layers[0][0].out_features // 2
+                if not (P - 16 < o_l < P) or o_l % 4:
+                    return None
+                W, b, lnw, lnb = (_pad_rows(p, P) for p in (W, b, lnw, lnb))
+                d.w_last_rows = P
+        keep += [W, b, lnw, lnb]
         d.W[l], d.b[l] = W.data_ptr(), b.data_ptr()
         if ln is not None:
-            d.ln_w[l], d.ln_b[l] = lnw_t.data_ptr(), lnb_t.data_ptr()
+            d.ln_w[l], d.ln_b[l] = lnw.data_ptr(), lnb.data_ptr()
             if eps is None:
                 eps = ln.eps
             elif eps != ln.eps:
                 return None
         else:
             d.ln_w[l] = d.ln_b[l] = None
-        d.width[l + 1] = lin.out_features
+        d.width[l + 1] = o_l
         d.act[l] = act
     d.ln_eps = float(eps)
     n_out = int(d.width[n])
     if skip is not None:
-        if tuple(skip.shape) != (M, n_out) or not skip.is_cuda or skip.dtype != torch.float32:
+        if tuple(skip.shape) != (M, n_out) or not skip.is_cuda or skip.dtype != dt:
             return None
         sk = skip if skip.is_contiguous() else skip.contiguous()
         keep.append(sk)
@@ -365,26 +395,26 @@ def clear_weight_cache(module: Optional[nn.Module] = None) -> None:
         _wcache.drop(list(module.parameters()))
 
 
-def _prepared_weight(weight, order, kept_cols):
-    """bf16 copy of a Linear weight (optionally only the column blocks of the segments that stay in the kernel's K
-    loop) in the kernel's fragment order, cached per weight object and version: an inference forward re-lays out
-    nothing, a training step once per optimizer update instead of once per call (forward + checkpoint recompute)"""
-    tag = (order.__name__, kept_cols)
+def _cached(weight, tag, make):
+    """``make()``, cached per weight object, version and layout ``tag`` (``_WeightCache``): an inference forward
+    re-lays out nothing, a training step once per optimizer update instead of once per call (forward + checkpoint
+    recompute); a new version replaces the old copy"""
     hit = _wcache.get(weight, tag)
-    if hit is not None:
-        return hit
-    W = weight.detach()
-    if kept_cols is not None:
-        W = torch.cat([W[:, c0:c1] for c0, c1 in kept_cols], dim=1)
-    W = order(W.to(torch.bfloat16).contiguous())
-    _wcache.put(weight, tag, W)     # one prepared copy per weight and layout: a new version replaces the old one
-    return W
+    if hit is None:
+        hit = make()
+        _wcache.put(weight, tag, hit)
+    return hit
 
 
-def _split_forward(d, out, dev):
-    """launch the wide-layer bf16 kernel the descriptor's weights were laid out for"""
-    _lib.check(_lib.load().hgnn_mlp_forward_bf16_split(ctypes.byref(d), _lib.ptr(out), _lib.current_stream(dev)),
-               "hgnn_mlp_forward_bf16_split")
+def _prepared_weight(weight, kept_cols):
+    """bf16 copy of a Linear weight (optionally only the column blocks of the segments that stay in the kernel's K
+    loop) in the kernel's fragment order"""
+    def make():
+        W = weight.detach()
+        if kept_cols is not None:
+            W = torch.cat([W[:, c0:c1] for c0, c1 in kept_cols], dim=1)
+        return _fragment_order(W.to(torch.bfloat16).contiguous())
+    return _cached(weight, ("_fragment_order", kept_cols), make)
 
 
 _fp32_split3 = os.environ.get("HGNN_FP32_SPLIT3", "1") != "0"
@@ -434,36 +464,39 @@ class training_forward:
         return False
 
 
-def _split3_on(net) -> bool:
-    if _ctx_training_forward.get() > 0 and not _opt("fp32_split3_train"):
+def _split3(net, train: bool = False) -> bool:
+    """the GEMMs of the fp32 MLP ``net`` are evaluated as split-bf16 products (hgnn_*_f32_split3).  ``train``: the
+    differentiable forward and the backward GEMMs.  First match wins:
+      1. under autograd (``train``) and in the no-grad pass of a checkpointed training step (``training_forward``): off
+         unless ``fp32_split3_train`` (set_fp32_split3_training, HGNN_FP32_SPLIT3_TRAIN=1);
+      2. an ``fp32_split3`` override of the current ``options`` context;
+      3. the module's own mark, ``hparams["fp32_gemm"]`` (``net._hgnn_split3``, models._mark_split3);
+      4. the process default (set_fp32_split3, HGNN_FP32_SPLIT3)."""
+    if (train or _ctx_training_forward.get() > 0) and not _opt("fp32_split3_train"):
         return False
     o = _ctx_options.get()
-    if o is not None and "fp32_split3" in o:        # an explicit context override outranks the per-module mark
+    if o is not None and "fp32_split3" in o:
         return bool(o["fp32_split3"])
-    flag = getattr(net, "_hgnn_split3", None)      # per-module override (hparams["fp32_gemm"])
+    flag = getattr(net, "_hgnn_split3", None)
     return _fp32_split3 if flag is None else bool(flag)
 
 
 def _split3_weight(weight, kept_cols, panels: bool, transpose: bool = False):
     """bf16 split stream of an fp32 Linear weight (per 32-wide k-chunk of the kept columns: W_hi, then W_mid) in
-    A-fragment order, cached per weight object and version (``_WeightCache``)"""
-    tag = ("split3", kept_cols, panels, transpose)
-    hit = _wcache.get(weight, tag)
-    if hit is not None:
-        return hit
-    W = weight.detach().float()
-    if kept_cols is not None:
-        W = torch.cat([W[:, c0:c1] for c0, c1 in kept_cols], dim=1)
-    if transpose:
-        W = W.t().contiguous()
-    hi = W.to(torch.bfloat16)
-    mid = (W - hi.float()).to(torch.bfloat16)
-    F, K = W.shape
-    # per 32-wide k-chunk: the chunk's W_hi columns, then its W_mid columns (virtual chunks 2c, 2c + 1)
-    Wv = torch.stack([hi.view(F, K // 32, 32), mid.view(F, K // 32, 32)], dim=2).reshape(F, 2 * K)
-    Wv = _fragment_order(Wv.contiguous())
-    _wcache.put(weight, tag, Wv)
-    return Wv
+    A-fragment order, cached per weight object and version (``_cached``)"""
+    def make():
+        W = weight.detach().float()
+        if kept_cols is not None:
+            W = torch.cat([W[:, c0:c1] for c0, c1 in kept_cols], dim=1)
+        if transpose:
+            W = W.t().contiguous()
+        hi = W.to(torch.bfloat16)
+        mid = (W - hi.float()).to(torch.bfloat16)
+        F, K = W.shape
+        # per 32-wide k-chunk: the chunk's W_hi columns, then its W_mid columns (virtual chunks 2c, 2c + 1)
+        Wv = torch.stack([hi.view(F, K // 32, 32), mid.view(F, K // 32, 32)], dim=2).reshape(F, 2 * K)
+        return _fragment_order(Wv.contiguous())
+    return _cached(weight, ("split3", kept_cols, panels, transpose), make)
 
 
 def _split3_linear(x: torch.Tensor, weight, cols, net) -> Optional[torch.Tensor]:
@@ -472,8 +505,7 @@ def _split3_linear(x: torch.Tensor, weight, cols, net) -> Optional[torch.Tensor]
     off / the shape has no instantiation (the caller then uses the library's fp32 GEMM)"""
     K = int(x.shape[1])
     N = int(weight.shape[1]) if cols is None else cols[1] - cols[0]
-    if not (_opt("fp32_split3_train") and _split3_on(net)) or x.dtype != torch.float32 or not x.is_cuda or K % 128 \
-            or N not in (256, 512) \
+    if not _split3(net, train=True) or x.dtype != torch.float32 or not x.is_cuda or K % 128 or N not in (256, 512) \
             or int(x.shape[0]) == 0:
         return None
     # the kernel wants the weight of the Linear that maps K -> N, i.e. W[:, cols]^T  [N, K]
@@ -510,47 +542,6 @@ def _split3_project(table: torch.Tensor, weight, cols_list):
     return outs
 
 
-def _split3_applies(net, segments, training: bool = False) -> bool:
-    """the opt-in split-bf16 path is switched on for this network and hgnn_mlp_forward_f32_split3 has its shape
-    (``training``: the call comes from the differentiable forward, which dumps the pre-LayerNorm rows)"""
-    if not _split3_on(net) or (training and not _opt("fp32_split3_train")):
-        return False
-    if not training and torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters()):
-        return False
-    layers = _parse(net)
-    if layers is None or len(layers) not in (2, 3) or any(ln is None for _, ln, _ in layers):
-        return False
-    if any(t.dtype != torch.float32 or int(t.shape[1]) % 128 for t, _ in segments):
-        return False
-    o = layers[-1][0].out_features
-    head_body = len(layers) == 2 and layers[0][0].out_features == o and o in (256, 512)
-    return head_body or (o in (128, 256) and all(lin.out_features == 2 * o for lin, _, _ in layers[:-1]))
-
-
-def _try_split3(net, segments, d, keep, training: bool = False):
-    """re-point a ready fp32 descriptor at split-3 weight streams if the opt-in path supports its shape"""
-    if not _split3_applies(net, segments, training) or int(d.w0_cols) != 0 or int(d.w_last_rows) != 0:
-        return False
-    layers = _parse(net)
-    kept = None
-    if int(d.n_pre):
-        # the columns of the segments that stayed in the kernel's K loop, in order
-        col, kept, proj = 0, [], _projected_segments(segments, int(d.M))
-        for i, (t, _) in enumerate(segments):
-            w = int(t.shape[1])
-            if i not in proj:
-                kept.append((col, col + w))
-            col += w
-        kept = tuple(kept)
-    for l, (lin, _, _) in enumerate(layers):
-        W = _split3_weight(lin.weight, kept if l == 0 else None, l == 0)
-        keep.append(W)
-        d.W[l] = W.data_ptr()
-    if not bool(_lib.load().hgnn_mlp_supported_f32_split3(ctypes.byref(d))):
-        raise RuntimeError("fused_concat_mlp: split-3 descriptor rejected")
-    return True
-
-
 _bf16_split = True
 
 
@@ -560,215 +551,147 @@ def set_bf16_split(flag: bool) -> None:
     _bf16_split = bool(flag)
 
 
-def _wants_split(net, segments) -> bool:
-    layers = _parse(net)
+def _wants_split(net, segments, layers=None) -> bool:
+    """the bf16 feature-split kernel's shapes (switch ``bf16_split``); ``layers``: ``_parse(net)`` when the caller has
+    it"""
+    layers = _parse(net) if layers is None else layers
     if not _opt("bf16_split") or layers is None or len(layers) not in (1, 2, 3):
         return False
     if any(int(t.shape[1]) % 128 for t, _ in segments):
         return False
-    widths = [lin.out_features for lin, _, _ in layers]
-    o = widths[-1]
+    o = layers[-1][0].out_features
     if len(layers) == 1:
-        return layers[0][1] is not None and o in (256, 512, 1024)  # single layers (chains)
-    return o in (128, 256, 512) and all(w == 2 * o for w in widths[:-1])
-
-
-def _descriptor_bf16(net, segments, skip, split=False, dry=False):
-    """descriptor for hgnn_mlp_forward_bf16 (bf16 rows, bf16 slot-ordered weights, fp32 bias / LayerNorm)
-    or, with ``split``, for hgnn_mlp_forward_bf16_split (weights in A-fragment order; gathered segments
-    of small tables pre-projected as in the fp32 path, P_s rounded once to bf16)"""
-    layers = _parse(net)
-    if layers is None or len(layers) not in (1, 2, 3) or not (1 <= len(segments) <= 3):
-        return None
-    if any(ln is None for _, ln, _ in layers):
-        return None
-    d = _lib.HgnnMlpDesc()
-    keep = []
-    M = None
-    for table, index in segments:
-        if table.dim() != 2 or not table.is_cuda or table.dtype != torch.bfloat16:
-            return None
-        rows = int(index.numel()) if index is not None else int(table.shape[0])
-        if M is None:
-            M = rows
-        elif M != rows:
-            return None
-    lin0 = layers[0][0]
-    if lin0.in_features != sum(int(t.shape[1]) for t, _ in segments) or not lin0.weight.is_cuda:
-        return None
-    want_pre = _opt("preproject_bf16")
-    if want_pre is None:
-        widths = [lin.out_features for lin, _, _ in layers]
-        want_pre = len(layers) > 1 and lin0.out_features >= 512
-    proj = _projected_segments(segments, M) if (split and want_pre) else []
-    col = n_kept = n_pre = 0
-    kept_cols = []
-    for i, (table, index) in enumerate(segments):
-        t = table if table.is_contiguous() else table.contiguous()
-        keep.append(t)
-        w = int(t.shape[1])
-        i32 = None
-        if index is not None:
-            i32 = get_index32(index, int(t.shape[0]))
-            keep.append(i32)
-        if i in proj:
-            if dry:
-                P = t
-            else:
-                with torch.autocast("cuda", enabled=False):
-                    # bf16 operands, fp32 accumulation, one rounding: the arithmetic the kernel's own MFMAs would do
-                    P = torch.matmul(t, lin0.weight.detach()[:, col:col + w].to(torch.bfloat16).t())
-                keep.append(P)
-            d.pre_table[n_pre] = P.data_ptr()
-            d.pre_index[n_pre] = i32.data_ptr() if i32.numel() else None
-            n_pre += 1
-        else:
-            d.seg_table[n_kept] = t.data_ptr()
-            d.seg_width[n_kept] = w
-            d.seg_index[n_kept] = (i32.data_ptr() if i32.numel() else None) if i32 is not None else None
-            kept_cols.append((col, col + w))
-            n_kept += 1
-        col += w
-    d.n_seg, d.n_pre = n_kept, n_pre
-    n = len(layers)
-    d.n_layers = n
-    d.width[0] = sum(c1 - c0 for c0, c1 in kept_cols)
-    eps = None
-    order = _fragment_order
-    for l, (lin, ln, act) in enumerate(layers):
-        if (l > 0 and lin.in_features != d.width[l]) or not lin.weight.is_cuda:
-            return None
-        W = lin.weight.detach()
-        if split:
-            k_in = sum(c1 - c0 for c0, c1 in kept_cols) if (l == 0 and n_pre) else W.shape[1]
-            if k_in % 32 or lin.out_features % 64:
-                return None
-            if not dry:
-                W = _prepared_weight(lin.weight, order, tuple(kept_cols) if (l == 0 and n_pre) else None)
-        else:
-            if l > 0:
-                if lin.in_features % 32:
-                    return None
-                W = W[:, _kslot_perm(lin.in_features, W.device)]
-            W = W.to(torch.bfloat16).contiguous()
-        small = [p.detach().float().contiguous() for p in (lin.bias, ln.weight, ln.bias)]
-        keep += [W] + small
-        d.W[l], d.b[l], d.ln_w[l], d.ln_b[l] = W.data_ptr(), small[0].data_ptr(), small[1].data_ptr(), small[2].data_ptr()
-        d.width[l + 1] = lin.out_features
-        d.act[l] = act
-        if eps is None:
-            eps = ln.eps
-        elif eps != ln.eps:
-            return None
-    d.ln_eps = float(eps)
-    n_out = int(d.width[n])
-    if skip is not None:
-        if tuple(skip.shape) != (M, n_out) or not skip.is_cuda or skip.dtype != torch.bfloat16:
-            return None
-        sk = skip if skip.is_contiguous() else skip.contiguous()
-        keep.append(sk)
-        d.skip = sk.data_ptr()
-    else:
-        d.skip = None
-    d.M = M
-    return d, keep, M, n_out
-
-
-def _layer_chain(net):
-    """fp32 MLPs too wide for one launch (latent 512: a 1024-wide hidden layer is 256 accumulators per lane): the
-    [Linear, LayerNorm, act] triples as single-layer Sequentials sharing the parameters (a plain last Linear -- the
-    width-1 heads -- stays a trailing ``nn.Linear``: an M x 1024 x 1 product), or None"""
-    layers = _parse(net)
-    if layers is None or len(layers) < 2 or any(ln is None for _, ln, _ in layers[:-1]):
-        return None
-    fused_layers = layers if layers[-1][1] is not None else layers[:-1]
-    if any(lin.out_features not in (512, 1024) or lin.in_features % 16 for lin, _, _ in fused_layers[1:]) \
-            or fused_layers[0][0].out_features not in (512, 1024):
-        return None
-    mods = list(net)
-    chain = [nn.Sequential(*mods[3 * i:3 * i + 3]) for i in range(len(fused_layers))]
-    if len(fused_layers) < len(layers):
-        chain.append(layers[-1][0])                      # the plain nn.Linear itself
-    return chain
-
-
-def _chain_supported(net, segments, skip) -> bool:
-    chain = _layer_chain(net)
-    if chain is None:
-        return False
-    bf16 = _is_bf16(segments)
-    try:
-        if bf16:
-            if not _wants_split(chain[0], segments):
-                return False
-            first = _descriptor_bf16(chain[0], segments, None, split=True, dry=True)
-            ok = first is not None and bool(_lib.load().hgnn_mlp_supported_bf16_split(ctypes.byref(first[0])))
-        else:
-            first = _descriptor(chain[0], segments, None, dry=True)
-            ok = first is not None and bool(_lib.load().hgnn_mlp_supported(ctypes.byref(first[0])))
-    except RuntimeError:
-        return False
-    if not ok:
-        return False
-    last = _parse(net)[-1][0]
-    if isinstance(chain[-1], nn.Linear) and skip is not None:
-        return False                                      # heads have no skip connection
-    dt = torch.bfloat16 if bf16 else torch.float32
-    return skip is None or (skip.is_cuda and skip.dtype == dt and tuple(skip.shape) == (first[2], last.out_features))
+        return layers[0][1] is not None and o in (256, 512, 1024)        # single layers (chains)
+    return o in (128, 256, 512) and all(lin.out_features == 2 * o for lin, _, _ in layers[:-1])
 
 
 def _is_bf16(segments) -> bool:
     return all(t.dtype == torch.bfloat16 for t, _ in segments)
 
 
-def supported(net, segments, skip, allow_chain: bool = True) -> bool:  # noqa: C901
-    """``allow_chain``: accept fp32 MLPs that run as one launch per layer (latent 512); a caller that has a cheaper
-    alternative for them (bf16 tail of the encoders in bf16 mode) passes False"""
-    if not _opt("enabled"):
-        return False
-    if _is_bf16(segments):
+class _Route(NamedTuple):
+    """what ``_run`` launches for one call (``_route``)"""
+    net: nn.Module
+    layers: list               # _parse(net)
+    entry: str                 # each launch calls hgnn_mlp_forward_<entry>: f32, f32_split3, bf16 or bf16_split
+    split_proj: bool = False   # f32_split3: pre-projections in the kernel's arithmetic (``_descriptor``)
+    chain: bool = False        # one launch per LayerNorm'ed layer (+ a trailing plain Linear)
+    head: bool = False         # score head: the plain last Linear runs outside the kernel, on the hidden rows
+    train: bool = False        # the differentiable variants (``_FusedMLPTrain``, ``_FusedMLPTrainBf16``)
+
+
+def _route(net, segments, skip, *, train: bool, allow_chain: bool = True) -> Optional[_Route]:  # noqa: C901
+    """The one dispatch decision: which fused kernel evaluates ``net`` on these arguments, or None (library path).
+    Parses ``net`` once and asks each kernel's own ``hgnn_mlp_supported*`` check at most once, on a dry descriptor.
+
+    ``train=False``: a forward autograd does not record (no grad mode, or nothing requires grad).  fp32 rows: the whole
+    network in one launch (hgnn_mlp_forward_f32), else -- ``allow_chain`` -- one launch per layer (latent 512; a caller
+    with a cheaper alternative, the bf16 tail of the encoders, passes False).  Among these, with the split-bf16
+    arithmetic on (``_split3``): score heads K -> H -> H -> w (H in 256, 512) run their hidden layers on
+    hgnn_mlp_forward_f32_split3 and the last Linear as a product over the hidden rows; networks of its shapes run whole
+    on it.  bf16 rows: the feature-split kernel where it wants the shape (``bf16_split``) else the plain bf16 kernel,
+    else the single-layer chain on the split kernel.
+    ``train=True``: autograd records.  fp32: the kernel's shapes with LayerNorm on every layer (f32_split3 when
+    ``_split3(net, train=True)``), and score heads (dumps of their hidden layers); bf16: the feature-split kernel."""
+    if train:
+        if not _opt("train_enabled") or not torch.is_grad_enabled():
+            return None
+    else:
+        if not _opt("enabled"):
+            return None
         if torch.is_grad_enabled():
             tensors = [t for t, _ in segments] + ([skip] if skip is not None else []) + list(net.parameters())
             if any(t.requires_grad for t in tensors):
-                return False
-        split = _wants_split(net, segments)
-        try:
-            desc = _descriptor_bf16(net, segments, skip, split, dry=True)
-        except RuntimeError:
-            return False
-        lib = _lib.load()
-        if desc is not None:
-            if split and bool(lib.hgnn_mlp_supported_bf16_split(ctypes.byref(desc[0]))):
-                return True
-            if not split and bool(lib.hgnn_mlp_supported_bf16(ctypes.byref(desc[0]))):
-                return True
-        return allow_chain and _chain_supported(net, segments, skip)
-    if torch.is_grad_enabled():
-        tensors = [t for t, _ in segments] + ([skip] if skip is not None else []) + list(net.parameters())
-        if any(t.requires_grad for t in tensors):
-            return False
-    try:
-        desc = _descriptor(net, segments, skip, dry=True)
-    except RuntimeError:
-        return False
-    if desc is not None and bool(_lib.load().hgnn_mlp_supported(ctypes.byref(desc[0]))):
-        return True
-    return allow_chain and _chain_supported(net, segments, skip)
-
-
-def _split3_head(net, segments, skip) -> bool:
-    """score heads (K -> H -> H -> w, plain last layer; IN.py:107-115, HGNN_GMM.py:313-321) under the opt-in
-    split-bf16 mode: the two LayerNorm'ed hidden layers run on hgnn_mlp_forward_f32_split3, the plain last Linear is
-    a trailing matrix-vector product over the hidden rows"""
-    if not _split3_on(net) or skip is not None:
-        return False
+                return None
     layers = _parse(net)
-    if layers is None or len(layers) != 3 or layers[2][1] is not None or layers[0][1] is None or layers[1][1] is None:
-        return False
-    h = layers[0][0].out_features
-    if h not in (256, 512) or layers[1][0].out_features != h or len(list(net)) != 7:
-        return False
-    return all(t.dtype == torch.float32 and int(t.shape[1]) % 128 == 0 for t, _ in segments)
+    if layers is None:
+        return None
+    lib = _lib.load()
+    bf16 = _is_bf16(segments)
+
+    def dry(entry, lays=layers, sk=skip):
+        """(dry descriptor or None, whether the kernel's own check accepts it)"""
+        try:
+            desc = _descriptor(net, segments, sk, entry, dry=True, layers=lays)
+        except RuntimeError:
+            return None, False
+        check = getattr(lib, "hgnn_mlp_supported" + ("" if entry == "f32" else "_" + entry))
+        return desc, desc is not None and bool(check(ctypes.byref(desc[0])))
+
+    def chain_ok():
+        """fp32 MLPs too wide for one launch (latent 512: a 1024-wide hidden layer is 256 accumulators per lane) and the
+        bf16 heads: the LayerNorm'ed layers one launch each, the rows of a plain last Linear (the width-1 heads) an
+        M x 1024 x w product"""
+        if len(layers) < 2 or any(ln is None for _, ln, _ in layers[:-1]):
+            return False
+        fused_layers = layers if layers[-1][1] is not None else layers[:-1]
+        if any(lin.out_features not in (512, 1024) or lin.in_features % 16 for lin, _, _ in fused_layers[1:]) \
+                or fused_layers[0][0].out_features not in (512, 1024):
+            return False
+        if bf16 and not _wants_split(None, segments, fused_layers[:1]):
+            return False
+        first, ok = dry("bf16_split" if bf16 else "f32", fused_layers[:1], None)
+        if not ok or (len(fused_layers) < len(layers) and skip is not None):
+            return False                                      # heads have no skip connection
+        dt = torch.bfloat16 if bf16 else torch.float32
+        return skip is None or (skip.is_cuda and skip.dtype == dt
+                                and tuple(skip.shape) == (first[2], layers[-1][0].out_features))
+
+    plain_last = layers[-1][1] is None
+    split3_shape = len(layers) in (2, 3) and all(ln is not None for _, ln, _ in layers) and \
+        all(t.dtype == torch.float32 and int(t.shape[1]) % 128 == 0 for t, _ in segments)
+    if split3_shape:
+        o = layers[-1][0].out_features
+        split3_shape = (len(layers) == 2 and layers[0][0].out_features == o and o in (256, 512)) or \
+            (o in (128, 256) and all(lin.out_features == 2 * o for lin, _, _ in layers[:-1]))     # head body or cell
+    if train:
+        if bf16:
+            if not _opt("train_bf16_enabled") or not _wants_split(net, segments, layers) \
+                    or any(lin.out_features not in (64, 128, 256, 512, 1024) for lin, _, _ in layers):
+                return None                               # widths of the bf16 LayerNorm / activation row kernels
+            return _Route(net, layers, "bf16_split", train=True) if dry("bf16_split")[1] else None
+        desc, ok = dry("f32")
+        # narrow encoders (zero-padded LayerNorm'ed last layer) have no dumps; the small-K encoders (w0_cols = 16: the
+        # kernel-side zero padding of W[0]) do -- their backward uses the unpadded parameters; score heads (plain last
+        # layer stored as 32 rows) dump their two hidden layers
+        head = len(layers) == 3 and plain_last
+        if not ok or (int(desc[0].w_last_rows) != 0 and not head):
+            return None
+        if head and (skip is not None or any(lin.out_features not in (64, 128, 256, 512) for lin, _, _ in layers[:2])):
+            return None                                   # widths of the LayerNorm / activation row kernels
+        split3 = not head and split3_shape and _split3(net, train=True)
+        return _Route(net, layers, "f32_split3" if split3 else "f32", head=head, train=True)
+    if bf16:
+        entry = "bf16_split" if _wants_split(net, segments, layers) else "bf16"
+        if dry(entry)[1]:
+            return _Route(net, layers, entry)
+        return _Route(net, layers, "bf16_split", chain=True) if allow_chain and chain_ok() else None
+    desc, ok = dry("f32")
+    chain = not ok and allow_chain and chain_ok()
+    if not ok and not chain:
+        return None
+    if _split3(net) and skip is None and len(layers) == 3 and plain_last \
+            and layers[0][0].out_features in (256, 512) and layers[1][0].out_features == layers[0][0].out_features \
+            and all(t.dtype == torch.float32 and int(t.shape[1]) % 128 == 0 for t, _ in segments):
+        # score heads (K -> H -> H -> w, IN.py:107-115, HGNN_GMM.py:313-321): the two LayerNorm'ed hidden layers on
+        # hgnn_mlp_forward_f32_split3, the plain last Linear a trailing matrix-vector product over the hidden rows
+        return _Route(net, layers, "f32_split3", split_proj=True, head=True)
+    if desc is not None and split3_shape and _split3(net):
+        return _Route(net, layers, "f32_split3", split_proj=True)
+    return _Route(net, layers, "f32", chain=chain)
+
+
+def supported(net, segments, skip, allow_chain: bool = True) -> bool:
+    """a fused kernel evaluates this no-grad call (``_route``).  ``allow_chain``: accept fp32 MLPs that run as one launch
+    per layer (latent 512); a caller that has a cheaper alternative for them (bf16 tail of the encoders in bf16 mode)
+    passes False"""
+    return _route(net, segments, skip, train=False, allow_chain=allow_chain) is not None
+
+
+def supported_train(net, segments, skip) -> bool:
+    """differentiable fused path (``_route``): cell networks (LayerNorm on every layer, 16-aligned segments) and score
+    heads; bf16 rows: the feature-split kernel's shapes at latent 128 / 256 (``_FusedMLPTrainBf16``)"""
+    return _route(net, segments, skip, train=True) is not None
 
 
 def _out_buffer(out, M, n_out, dtype, dev):
@@ -781,66 +704,73 @@ def _out_buffer(out, M, n_out, dtype, dev):
     return out
 
 
-def fused_concat_mlp(net, segments, skip: Optional[torch.Tensor], out: Optional[torch.Tensor] = None):
-    """``out``: write the result rows into this tensor (no-grad callers that assemble one edge table from several
-    calls -- the interior / boundary split of a sharded edge update -- avoid a 2 GB concatenation); only the
-    single-launch paths take it"""
-    bf16 = _is_bf16(segments)
-    if not bf16 and _split3_head(net, segments, skip):
-        mods = list(net)
-        body = nn.Sequential(*mods[:6])
-        body._hgnn_split3 = True
-        hid = fused_concat_mlp(body, segments, None)
-        res = torch.nn.functional.linear(hid, mods[6].weight, mods[6].bias)
-        return res if out is None else out.copy_(res)
-    if len(_parse(net) or []) > 1:
-        if bf16:
-            sp = _wants_split(net, segments)
-            whole = _descriptor_bf16(net, segments, skip, sp, dry=True)
-            whole_ok = whole is not None and bool((_lib.load().hgnn_mlp_supported_bf16_split if sp else
-                                                   _lib.load().hgnn_mlp_supported_bf16)(ctypes.byref(whole[0])))
-        else:
-            whole = _descriptor(net, segments, skip, dry=True)
-            whole_ok = whole is not None and (bool(_lib.load().hgnn_mlp_supported(ctypes.byref(whole[0])))
-                                              or _split3_applies(net, segments))
-        if not whole_ok and _chain_supported(net, segments, skip):
-            # one launch per layer; the hidden rows make one trip through HBM (fp32 at latent 512)
-            chain = _layer_chain(net)
-            segs, out_c = segments, None
-            for i, sub in enumerate(chain):
-                if isinstance(sub, nn.Linear):
-                    out_c = torch.nn.functional.linear(out_c, sub.weight.to(out_c.dtype), sub.bias.to(out_c.dtype))
-                else:
-                    out_c = fused_concat_mlp(sub, segs, skip if i == len(chain) - 1 else None)
-                    segs = [(out_c, None)]
-            return out_c if out is None else out.copy_(out_c)
-    split = bf16 and _wants_split(net, segments)
-    desc = _descriptor_bf16(net, segments, skip, split) if bf16 else \
-        _descriptor(net, segments, skip, split_proj=_split3_applies(net, segments))
+def _forward(entry, d, out, dev):
+    """launch hgnn_mlp_forward_<entry> on a ready descriptor"""
+    name = "hgnn_mlp_forward_" + entry
+    _lib.check(getattr(_lib.load(), name)(ctypes.byref(d), _lib.ptr(out), _lib.current_stream(dev)), name)
+    if entry == "f32_split3":
+        stats["split3_calls"] = stats.get("split3_calls", 0) + 1
+
+
+def _launch(layers, segments, skip, entry, split_proj=False, out=None):
+    """one no-grad launch of hgnn_mlp_forward_<entry>"""
+    desc = _descriptor(None, segments, skip, entry, split_proj, layers=layers)
     if desc is None:
         raise RuntimeError("fused_concat_mlp: unsupported arguments (call supported() first)")
     d, keep, M, n_out = desc
     dev = segments[0][0].device
-    out = _out_buffer(out, M, n_out, torch.bfloat16 if bf16 else torch.float32, dev)
+    out = _out_buffer(out, M, n_out, torch.bfloat16 if entry.startswith("bf16") else torch.float32, dev)
     if M == 0:
         return out
-    lib = _lib.load()
     with torch.cuda.device(dev):
-        if split:
-            _split_forward(d, out, dev)
-        elif bf16:
-            _lib.check(lib.hgnn_mlp_forward_bf16(ctypes.byref(d), _lib.ptr(out), _lib.current_stream(dev)),
-                       "hgnn_mlp_forward_bf16")
-        elif _try_split3(net, segments, d, keep):
-            _lib.check(lib.hgnn_mlp_forward_f32_split3(ctypes.byref(d), _lib.ptr(out), _lib.current_stream(dev)),
-                       "hgnn_mlp_forward_f32_split3")
-            stats["split3_calls"] = stats.get("split3_calls", 0) + 1
-        else:
-            _lib.check(lib.hgnn_mlp_forward_f32(ctypes.byref(d), _lib.ptr(out), _lib.current_stream(dev)),
-                       "hgnn_mlp_forward_f32")
+        _forward(entry, d, out, dev)
     del keep
     stats["fused_calls"] += 1
     return out
+
+
+def _run(r: _Route, segments, skip, out=None):
+    """evaluate ``net`` (+ ``skip``) on ``segments`` the way route ``r`` says.  ``out``: write the result rows into this
+    tensor (no-grad callers that assemble one edge table from several calls -- the interior / boundary split of a sharded
+    edge update -- avoid a 2 GB concatenation); only the single-launch paths write into it directly"""
+    layers = r.layers
+    if r.train:
+        tables, indices = [t for t, _ in segments], tuple(i for _, i in segments)
+        params = []
+        for lin, ln, _ in layers[:2] if r.head else layers:
+            params += [lin.weight, lin.bias, ln.weight, ln.bias]
+        if r.head:
+            # score heads (IN.py:107-115,126-127; HGNN_GMM.py:313-321,342-344) under autograd: the two LayerNorm'ed
+            # hidden layers on the differentiable fused kernel (dumps + hand-written backward), the plain last Linear --
+            # an [M, H] x [H, w<=32] product -- applied to the returned hidden rows
+            hidden = _FusedMLPTrain.apply(r, indices, False, *tables, *params)
+            stats["fused_head_train_calls"] = stats.get("fused_head_train_calls", 0) + 1
+            return torch.nn.functional.linear(hidden, layers[2][0].weight, layers[2][0].bias)
+        fn = _FusedMLPTrainBf16 if r.entry == "bf16_split" else _FusedMLPTrain
+        return fn.apply(r, indices, skip is not None, *tables, *([skip] if skip is not None else []), *params)
+    if r.head:
+        y = _launch(layers[:2], segments, None, r.entry, r.split_proj)
+        y = torch.nn.functional.linear(y, layers[2][0].weight, layers[2][0].bias)
+    elif r.chain:
+        # one launch per layer; the hidden rows make one trip through HBM (fp32 at latent 512)
+        y = None
+        for i, layer in enumerate(layers):
+            if layer[1] is None:                          # the plain last Linear of a head
+                y = torch.nn.functional.linear(y, layer[0].weight.to(y.dtype), layer[0].bias.to(y.dtype))
+            else:
+                y = _launch([layer], segments, skip if i == len(layers) - 1 else None, r.entry)
+                segments = [(y, None)]
+    else:
+        return _launch(layers, segments, skip, r.entry, r.split_proj, out)
+    return y if out is None else out.copy_(y)
+
+
+def fused_concat_mlp(net, segments, skip: Optional[torch.Tensor], out: Optional[torch.Tensor] = None):
+    """no-grad evaluation on the kernel ``_route`` picks.  ``out``: see ``_run``"""
+    r = _route(net, segments, skip, train=False)
+    if r is None:
+        raise RuntimeError("fused_concat_mlp: unsupported arguments (call supported() first)")
+    return _run(r, segments, skip, out)
 
 
 # --------------------------------------------------------------------------- training variant
@@ -884,7 +814,7 @@ def _atb(A: torch.Tensor, B: torch.Tensor, net=None) -> torch.Tensor:
     8 GFLOP of n = 120k, ~110 TFLOP/s at n = 2M); a batched product over row blocks plus one sum fills the
     chip (fixed summation order: deterministic).  EC-IN training step 368 -> 306 ms."""
     n = int(A.shape[0])
-    if net is not None and _opt("fp32_split3_train") and _split3_on(net) and n >= 4096 and A.dtype == torch.float32 and B.dtype == torch.float32 \
+    if net is not None and _split3(net, train=True) and n >= 4096 and A.dtype == torch.float32 and B.dtype == torch.float32 \
             and A.is_cuda and int(A.shape[1]) % 8 == 0 and int(B.shape[1]) % 8 == 0:
         from .ops import wgrad_f32_split3
         stats["split3_wgrad_calls"] = stats.get("split3_wgrad_calls", 0) + 1
@@ -919,21 +849,20 @@ class _FusedMLPTrain(torch.autograd.Function):
     also be switched off (hparams["checkpointing"]=False) and the dumps kept instead."""
 
     @staticmethod
-    def forward(ctx, net, indices, has_skip, *tensors):
+    def forward(ctx, route, indices, has_skip, *tensors):
         n_seg = len(indices)
         tables = list(tensors[:n_seg])
         skip = tensors[n_seg] if has_skip else None
         params = tensors[n_seg + (1 if has_skip else 0):]
         segments = [(t, i) for t, i in zip(tables, indices)]
-        desc = _descriptor(net, segments, skip)
+        desc = _descriptor(route.net, segments, skip, route.entry, layers=route.layers)
         if desc is None:
             raise RuntimeError("fused_concat_mlp_train: unsupported arguments (call supported_train() first)")
         d, keep, M, n_out = desc
         n = int(d.n_layers)
-        head = int(d.w_last_rows) == 32 and _parse(net)[-1][1] is None
-        if head:
+        if route.head:
             n -= 1             # a score head: the LayerNorm'ed hidden layers are differentiated here, the plain last
-                               # Linear is applied by the caller on the returned hidden rows (``fused_head_train``)
+                               # Linear is applied by the caller on the returned hidden rows (``_run``)
         dev = tables[0].device
         zs = [torch.empty((M, int(d.width[l + 1])), dtype=torch.float32, device=dev) for l in range(n)]
         for l in range(n):
@@ -941,26 +870,19 @@ class _FusedMLPTrain(torch.autograd.Function):
         out = torch.empty((M, n_out), dtype=torch.float32, device=dev)
         if M:
             with torch.cuda.device(dev):
-                if not head and _try_split3(net, segments, d, keep, training=True):
-                    # opt-in: the forward (and its dumps) on the split-bf16 kernel; the backward below is unchanged
-                    _lib.check(_lib.load().hgnn_mlp_forward_f32_split3(ctypes.byref(d), _lib.ptr(out),
-                                                                       _lib.current_stream(dev)),
-                               "hgnn_mlp_forward_f32_split3")
-                    stats["split3_calls"] = stats.get("split3_calls", 0) + 1
-                else:
-                    _lib.check(_lib.load().hgnn_mlp_forward_f32(ctypes.byref(d), _lib.ptr(out),
-                                                                _lib.current_stream(dev)), "hgnn_mlp_forward_f32")
+                # f32_split3 (opt-in): the forward and its dumps on the split-bf16 kernel; the backward is unchanged
+                _forward(route.entry, d, out, dev)
         del keep
         stats["fused_train_calls"] += 1
         ctx.indices, ctx.has_skip, ctx.n = indices, has_skip, n
-        ctx.net = net
+        ctx.net, ctx.layers = route.net, route.layers
         ctx.acts = [int(d.act[l]) for l in range(n)]
         ctx.eps = float(d.ln_eps)
         ctx.save_for_backward(*tables, *params, *zs)
-        if head:
+        if route.head:
             # the hidden rows feeding the plain last Linear: one LayerNorm / activation row pass over the last dump
-            lays = _parse(net)
-            return _ln_act_forward(zs[n - 1], lays[n - 1][1].weight, lays[n - 1][1].bias, ctx.acts[n - 1], ctx.eps)
+            ln = route.layers[n - 1][1]
+            return _ln_act_forward(zs[n - 1], ln.weight, ln.bias, ctx.acts[n - 1], ctx.eps)
         return out
 
     @staticmethod
@@ -981,7 +903,7 @@ class _FusedMLPTrain(torch.autograd.Function):
         if int(grad_out.shape[0]) == 0:
             return _zero_grads(ctx, tables, params, grad_out, n_seg)
         W = [params[4 * l] for l in range(n)]
-        lw = [lin.weight for lin, _, _ in _parse(ctx.net)][:n]   # the Parameter objects themselves (weight-prep cache keys)
+        lw = [lin.weight for lin, _, _ in ctx.layers[:n]]   # the Parameter objects themselves (weight-prep cache keys)
         lnw = [params[4 * l + 2] for l in range(n)]
         lnb = [params[4 * l + 3] for l in range(n)]
         aten = torch.ops.aten
@@ -1067,95 +989,21 @@ class _FusedMLPTrain(torch.autograd.Function):
         return (None, None, None, *grads_tables, *grad_skip, *grads_params)
 
 
-def supported_train(net, segments, skip) -> bool:
-    """differentiable fused path: cell networks (LayerNorm on every layer, 16-aligned segments); bf16 rows:
-    the feature-split kernel's shapes at latent 128 / 256 (``_FusedMLPTrainBf16``)"""
-    if not _opt("train_enabled") or not torch.is_grad_enabled():
-        return False
-    if _is_bf16(segments):
-        if not _opt("train_bf16_enabled") or not _wants_split(net, segments):
-            return False
-        layers = _parse(net)
-        if any(lin.out_features not in (64, 128, 256, 512, 1024) for lin, _, _ in layers):
-            return False                              # widths of the bf16 LayerNorm / activation row kernels
-        try:
-            desc = _descriptor_bf16(net, segments, skip, split=True, dry=True)
-        except RuntimeError:
-            return False
-        return desc is not None and bool(_lib.load().hgnn_mlp_supported_bf16_split(ctypes.byref(desc[0])))
-    try:
-        desc = _descriptor(net, segments, skip, dry=True)
-    except RuntimeError:
-        return False
-    if desc is None:
-        return False
-    d = desc[0]
-    # narrow encoders (zero-padded LayerNorm'ed last layer) have no dumps; the small-K encoders (w0_cols = 16: the
-    # kernel-side zero padding of W[0]) do -- their backward uses the unpadded parameters; score heads (plain last
-    # layer stored as 32 rows) dump their two hidden layers (``fused_head_train``)
-    if int(d.w_last_rows) != 0 and not _is_head(net):
-        return False
-    if _is_head(net) and (skip is not None or any(int(d.width[l + 1]) not in (64, 128, 256, 512) for l in range(2))):
-        return False                                   # widths of the LayerNorm / activation row kernels
-    return bool(_lib.load().hgnn_mlp_supported(ctypes.byref(d)))
-
-
-def _is_head(net) -> bool:
-    layers = _parse(net)
-    return layers is not None and len(layers) == 3 and layers[2][1] is None and layers[0][1] is not None \
-        and layers[1][1] is not None and layers[2][0].out_features <= 32
-
-
 def fused_concat_mlp_train(net, segments, skip: Optional[torch.Tensor]):
-    layers = _parse(net)
-    if not _is_bf16(segments) and _is_head(net):
-        # score heads (IN.py:107-115,126-127; HGNN_GMM.py:313-321,342-344) under autograd: the two LayerNorm'ed hidden
-        # layers on the differentiable fused kernel (dumps + hand-written backward), the plain last Linear -- an
-        # [M, H] x [H, w<=32] product -- applied to the returned hidden rows
-        body = layers[:2]
-        params = []
-        for lin, ln, _ in body:
-            params += [lin.weight, lin.bias, ln.weight, ln.bias]
-        hidden = _FusedMLPTrain.apply(net, tuple(i for _, i in segments), False, *[t for t, _ in segments], *params)
-        last = layers[2][0]
-        stats["fused_head_train_calls"] = stats.get("fused_head_train_calls", 0) + 1
-        return torch.nn.functional.linear(hidden, last.weight, last.bias)
-    params = []
-    for lin, ln, _ in layers:
-        params += [lin.weight, lin.bias, ln.weight, ln.bias]
-    tables = [t for t, _ in segments]
-    indices = tuple(i for _, i in segments)
-    extra = [skip] if skip is not None else []
-    fn = _FusedMLPTrainBf16 if _is_bf16(segments) else _FusedMLPTrain
-    return fn.apply(net, indices, skip is not None, *tables, *extra, *params)
+    """differentiable evaluation on the kernel ``_route`` picks"""
+    r = _route(net, segments, skip, train=True)
+    if r is None:
+        raise RuntimeError("fused_concat_mlp_train: unsupported arguments (call supported_train() first)")
+    return _run(r, segments, skip)
 
 
 # --------------------------------------------------------------------------- bf16 training variant
 _train_bf16_enabled = True
-_wgrad_hip = True          # A/B: hand-written split-K bf16-MFMA weight gradient vs the library's TN GEMM
 
 
-def set_train_bf16(flag: bool, wgrad_hip: bool = True) -> None:
-    global _train_bf16_enabled, _wgrad_hip
-    _train_bf16_enabled, _wgrad_hip = bool(flag), bool(wgrad_hip)
-
-
-def _wgrad(dz: torch.Tensor, rows: torch.Tensor, colsum: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fp32 dz^T rows of bf16 operands (+ optionally dz's column sums = the bias gradient, from the same pass)"""
-    if _opt("wgrad_hip"):
-        from .ops import wgrad_bf16
-        return wgrad_bf16(dz, rows, colsum=colsum)
-    if colsum is not None:
-        colsum.copy_(dz.float().sum(dim=0))
-    return (dz.t() @ rows).float()
-
-
-_bwd_fused = True          # A/B: hand-written fused data gradient (hgnn_mlp_backward_layer_bf16) vs library GEMM + row passes
-
-
-def set_bwd_fused(flag: bool) -> None:
-    global _bwd_fused
-    _bwd_fused = bool(flag)
+def set_train_bf16(flag: bool) -> None:
+    global _train_bf16_enabled
+    _train_bf16_enabled = bool(flag)
 
 
 def _bwd_layer_supported(K: int, N: int) -> bool:
@@ -1210,13 +1058,13 @@ class _FusedMLPTrainBf16(torch.autograd.Function):
               as in the fp32 variant (N-row products instead of M-row ones)."""
 
     @staticmethod
-    def forward(ctx, net, indices, has_skip, *tensors):
+    def forward(ctx, route, indices, has_skip, *tensors):
         n_seg = len(indices)
         tables = list(tensors[:n_seg])
         skip = tensors[n_seg] if has_skip else None
         params = tensors[n_seg + (1 if has_skip else 0):]
         segments = [(t, i) for t, i in zip(tables, indices)]
-        desc = _descriptor_bf16(net, segments, skip, split=True)
+        desc = _descriptor(route.net, segments, skip, route.entry, layers=route.layers)
         if desc is None:
             raise RuntimeError("fused_concat_mlp_train (bf16): unsupported arguments (call supported_train() first)")
         d, keep, M, n_out = desc
@@ -1228,7 +1076,7 @@ class _FusedMLPTrainBf16(torch.autograd.Function):
         out = torch.empty((M, n_out), dtype=torch.bfloat16, device=dev)
         if M:
             with torch.cuda.device(dev):
-                _split_forward(d, out, dev)
+                _forward(route.entry, d, out, dev)
         del keep
         stats["fused_train_calls"] += 1
         ctx.indices, ctx.has_skip, ctx.n = indices, has_skip, n
@@ -1252,6 +1100,7 @@ class _FusedMLPTrainBf16(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, grad_out):
+        from .ops import wgrad_bf16
         from .plan import get_plan
         n, indices = ctx.n, ctx.indices
         n_seg = len(indices)
@@ -1277,24 +1126,24 @@ class _FusedMLPTrainBf16(torch.autograd.Function):
         for l in range(n - 1, 0, -1):
             K, N = int(W[l].shape[0]), int(W[l].shape[1])
             need_bias = grads_params[4 * l + 1] is None
-            colsum = torch.empty(K, dtype=torch.float32, device=dz.device) if need_bias and _opt("wgrad_hip") else None
-            if _opt("bwd_fused") and _bwd_layer_supported(K, N):
+            colsum = torch.empty(K, dtype=torch.float32, device=dz.device) if need_bias else None
+            if _bwd_layer_supported(K, N):
                 # hand-written data gradient fused with the LayerNorm / activation backward of the layer below
                 dz_prev, a_prev, dlw, dlb = _bwd_layer(dz, W[l], zs[l - 1], lnw[l - 1], lnb[l - 1], ctx.acts[l - 1],
                                                        ctx.eps, want_a=True)
-                grads_params[4 * l] = _wgrad(dz, a_prev, colsum).to(pdt[l])
+                grads_params[4 * l] = wgrad_bf16(dz, a_prev, colsum=colsum).to(pdt[l])
                 del a_prev
                 dbias_prev = None                                         # comes out of layer l-1's weight gradient
             else:
                 a_prev = _ln_act_forward(zs[l - 1], lnw[l - 1], lnb[l - 1], ctx.acts[l - 1], ctx.eps)
-                grads_params[4 * l] = _wgrad(dz, a_prev, colsum).to(pdt[l])
+                grads_params[4 * l] = wgrad_bf16(dz, a_prev, colsum=colsum).to(pdt[l])
                 del a_prev
                 da = dz @ W[l].detach().to(bf)                            # data gradient: bf16 library GEMM
                 dz_prev, dlw, dlb, dbias_prev = _ln_act_backward(zs[l - 1], da, lnw[l - 1], lnb[l - 1],
                                                                  ctx.acts[l - 1], ctx.eps)
                 del da
             if need_bias:
-                grads_params[4 * l + 1] = (colsum if colsum is not None else dz.float().sum(dim=0)).to(pdt[l])
+                grads_params[4 * l + 1] = colsum.to(pdt[l])
             grads_params[4 * (l - 1) + 2] = dlw.to(pdt[l - 1])
             grads_params[4 * (l - 1) + 3] = dlb.to(pdt[l - 1])
             if dbias_prev is not None:
@@ -1313,21 +1162,19 @@ class _FusedMLPTrainBf16(torch.autograd.Function):
             W_s = W0[:, col:col + w_s]
             if idx is not None:
                 S = _seg_reduce_wide(get_plan(idx, int(tab.shape[0])), dz)
-                dW[:, col:col + w_s] = _wgrad(S, tab)
+                dW[:, col:col + w_s] = wgrad_bf16(S, tab)
                 if ctx.needs_input_grad[3 + s_i]:
                     grads_tables[s_i] = S @ W_s
                 del S
             else:
-                colsum = None
-                if need_bias and _opt("wgrad_hip"):
-                    colsum = torch.empty(H0, dtype=torch.float32, device=dz.device)
-                dW[:, col:col + w_s] = _wgrad(dz, tab, colsum)
-                if colsum is not None:
+                colsum = torch.empty(H0, dtype=torch.float32, device=dz.device) if need_bias else None
+                dW[:, col:col + w_s] = wgrad_bf16(dz, tab, colsum=colsum)
+                if need_bias:
                     grads_params[1] = colsum.to(pdt[0])
                     need_bias = False
                 if ctx.needs_input_grad[3 + s_i]:
                     folded = ctx.skip_seg == s_i          # edges + MLP(..., edges): both gradients in one epilogue
-                    if _opt("bwd_fused") and _bwd_layer_supported(H0, w_s):
+                    if _bwd_layer_supported(H0, w_s):
                         grads_tables[s_i] = _bwd_layer(dz, W[0][:, col:col + w_s], None, None, None, 0, ctx.eps,
                                                        skip=g if folded else None)[0]
                     elif folded:

@@ -34,23 +34,26 @@ def concat_mlp(net: nn.Sequential, segments: Sequence[Segment], skip: Optional[t
         # otherwise evaluated as usual and copied
         if torch.is_grad_enabled() and any(t.requires_grad for t, _ in segments):
             raise RuntimeError("concat_mlp(out=...) is a no-grad path")
-        if not bf16_tail and fused.supported(net, segments, skip):
-            return fused.fused_concat_mlp(net, segments, skip, out=out)
+        r = None if bf16_tail else fused._route(net, segments, skip, train=False)
+        if r is not None:
+            return fused._run(r, segments, skip, out=out)
         return out.copy_(concat_mlp(net, segments, skip, bf16_tail))
-    if bf16_tail and skip is None and len(net) > 3 and not torch.is_grad_enabled() and fused._opt("enabled"):
+    if bf16_tail and skip is None and len(net) > 3 and not torch.is_grad_enabled() and fused._opt("enabled") \
+            and all(t.dtype == torch.float32 for t, _ in segments):
         # bf16 latent mode, encoders: hybrid chain -- the first Linear (hit coordinates: must not be rounded to 8
         # bits) as ONE fp32 fused layer, the wide tail on the bf16 feature-split kernel (edge encoder at latent 256,
         # 2M rows: 3.0 instead of 5.6 ms for the all-fp32 fused kernel)
         first, rest = nn.Sequential(*list(net)[:3]), nn.Sequential(*list(net)[3:])
-        if all(t.dtype == torch.float32 for t, _ in segments) and fused.supported(first, segments, None):
-            probe = [(torch.empty((0, net[0].out_features), dtype=torch.bfloat16, device=segments[0][0].device), None)]
-            if fused.supported(rest, probe, None):
-                y = fused.fused_concat_mlp(first, segments, None)
-                return fused.fused_concat_mlp(rest, [(y.to(torch.bfloat16), None)], None)
-    if fused.supported(net, segments, skip, allow_chain=not bf16_tail):
-        return fused.fused_concat_mlp(net, segments, skip)
-    if fused.supported_train(net, segments, skip):
-        return fused.fused_concat_mlp_train(net, segments, skip)
+        r_first = fused._route(first, segments, None, train=False)
+        probe = [(torch.empty((0, net[0].out_features), dtype=torch.bfloat16, device=segments[0][0].device), None)]
+        r_rest = None if r_first is None else fused._route(rest, probe, None, train=False)
+        if r_rest is not None:
+            y = fused._run(r_first, segments, None)
+            return fused._run(r_rest, [(y.to(torch.bfloat16), None)], None)
+    r = fused._route(net, segments, skip, train=False, allow_chain=not bf16_tail) \
+        or fused._route(net, segments, skip, train=True)
+    if r is not None:
+        return fused._run(r, segments, skip)
     parts: List[torch.Tensor] = []
     for table, index in segments:
         parts.append(table if index is None else gather_rows(table, index))

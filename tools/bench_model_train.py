@@ -55,20 +55,5 @@ for name, on in (("hip", True), ("library", False))[:1 if os.environ.get("TRAIN_
     res[f"loss_{name}"] = loss
     res[f"peak_mem_GB_{name}"] = torch.cuda.max_memory_allocated() / 2**30
 fused.set_enabled(True)
-if bf16 and os.environ.get("TRAIN_WGRAD_AB"):
-    fused.set_train_bf16(True, wgrad_hip=False)          # A/B: the library's TN GEMM for the weight gradients
-    step()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(3):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        step()
-        b.record()
-        torch.cuda.synchronize()
-        ts.append(a.elapsed_time(b))
-    ts.sort()
-    res["train_step_hip_with_library_wgrad_ms"] = ts[1]
-    fused.set_train_bf16(True, wgrad_hip=True)
 res["events_per_s_hip"] = 1e3 / res["train_step_hip_ms"]
 print(json.dumps(res, indent=1))

@@ -24,12 +24,11 @@ segs = [(direct, None)]
 
 def run(v):
     _lib.check(lib.hgnn_set_option(b"mlp_split3_rows128", v))
-    d, keep, M_, n_out = fused._descriptor(net, segs, direct)
+    d, keep, M_, n_out = fused._descriptor(net, segs, direct, "f32_split3")
     zs = [torch.empty((M, int(d.width[l + 1])), dtype=torch.float32, device="cuda") for l in range(2)]
     for l in range(2):
         d.save_pre[l] = zs[l].data_ptr()
     out = torch.empty((M, n_out), dtype=torch.float32, device="cuda")
-    assert fused._try_split3(net, segs, d, keep, training=True)
     _lib.check(lib.hgnn_mlp_forward_f32_split3(ctypes.byref(d), _lib.ptr(out), _lib.current_stream(direct.device)))
     torch.cuda.synchronize()
     return zs[0], zs[1], out
