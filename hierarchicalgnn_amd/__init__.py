@@ -3,6 +3,7 @@ hierarchical GNN (reference: clairesonglee/HierarchicalGNN).
 
 Drop-in surface (same names / signatures as the reference):
     scatter_add(src, index, dim=0, dim_size=N)          <- torch_scatter.scatter_add
+    scatter_min / scatter_max / scatter_mean / scatter   <- torch_scatter (same names)
     InteractionGNNCell(hparams), HierarchicalGNNCell(hparams)   <- Modules/gnn_utils.py
     make_mlp(...)                                        <- Modules/utils.py
 
@@ -11,6 +12,7 @@ libhgnn_hip.so through the C ABI of include/hgnn_hip.h; there is no CPU or
 eager fallback.
 """
 from .ops import scatter_add, gather_scale_scatter, gather_rows, l1_row_scale  # noqa: F401
+from .ops import scatter, scatter_max, scatter_mean, scatter_min  # noqa: F401
 from .plan import GraphPlan, get_plan, clear_plan_cache, plan_cache_stats  # noqa: F401
 from .utils import make_mlp  # noqa: F401
 from .gnn_utils import InteractionGNNCell, HierarchicalGNNCell  # noqa: F401

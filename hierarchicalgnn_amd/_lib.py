@@ -17,10 +17,12 @@ LIB_PATH = os.environ.get("HGNN_LIB") or os.path.join(_HERE, "csrc", "libhgnn_hi
 
 HGNN_OK = 0
 CNT_WORK, CNT_SPLIT, CNT_PARTIAL, CNT_ERR, CNT_VALID, CNT_UNSORTED = 0, 1, 2, 3, 4, 5
-ABI_VERSION = 23
+ABI_VERSION = 24
 MLP_BWD_BLOCKS = 512   # HGNN_MLP_BWD_BLOCKS
 GMM_STATE, GMM_BLOCKS = 16, 1024   # HGNN_GMM_STATE, HGNN_GMM_BLOCKS
 LN_ACT_BLOCKS = 1024   # HGNN_LN_ACT_BLOCKS
+RED_SUM, RED_MIN, RED_MAX = 0, 1, 2   # HGNN_RED_*
+DT_F32, DT_BF16, DT_I32, DT_I64 = 0, 1, 2, 3   # HGNN_DT_*
 
 
 class HgnnPlan(Structure):
@@ -65,6 +67,9 @@ _SIGNATURES = {
     "hgnn_plan_build": (c_int, [c_void_p, c_void_p, POINTER(HgnnPlan), c_void_p, c_size_t, c_void_p]),
     "hgnn_segment_reduce_f32": (c_int, [POINTER(HgnnPlan), c_void_p, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+    "hgnn_segment_reduce_ex": (c_int, [POINTER(HgnnPlan), c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "hgnn_segment_arg_backward": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "hgnn_gather_rows_f32": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
     "hgnn_spread_rows_f32": (c_int, [POINTER(HgnnPlan), c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),

@@ -146,17 +146,24 @@ def scatter_add(src: torch.Tensor, index: torch.Tensor, dim: int = 0, dim_size: 
                 validate: bool = True) -> torch.Tensor:
     """torch_scatter.scatter_add for the call shape the reference uses.
 
-    src   Tensor[M, ...] float32; index LongTensor[M] (broadcast along features); dim must be 0.
-    Returns a freshly allocated Tensor[dim_size, ...] with zero rows for absent
-    destinations.  Differentiable w.r.t. ``src`` (and ``weight``).
+    src   Tensor[M, ...] float32 / bfloat16, or int32 / int64 (exact, wrapping integer sum);
+    index LongTensor[M] (broadcast along features).  ``dim`` other than 0 moves that dimension to the
+    front and back again.  Returns a freshly allocated Tensor[dim_size, ...] with zero rows for absent
+    destinations.  Differentiable w.r.t. floating-point ``src`` (and ``weight``).
     ``weight`` (Tensor[M] or [M,1]) is an extension: fused ``scatter_add(src*weight, ...)``
     as at Modules/gnn_utils.py:143.  ``validate=False`` (an index this package produced itself, known to
     be in range) skips the one host read a new plan makes to raise on out-of-range entries.
     """
-    if dim != 0 and dim != -src.dim():
-        raise RuntimeError("hierarchicalgnn_amd.scatter_add: only dim=0 is implemented (the reference's use)")
     if out is not None:
         raise RuntimeError("hierarchicalgnn_amd.scatter_add: `out=` is not supported")
+    if src.dtype in _INT_DTYPES:
+        if weight is not None:
+            raise RuntimeError("hierarchicalgnn_amd.scatter_add: `weight` needs floating-point src")
+        return _scatter_ex(src, index, dim, dim_size, plan, validate, _lib.RED_SUM, "scatter_add")[0]
+    d = _norm_dim(dim, src.dim(), "scatter_add")
+    if d != 0:
+        return scatter_add(src.movedim(d, 0), index, 0, dim_size, plan=plan, weight=weight,
+                           validate=validate).movedim(0, d)
     _require_hip(src, "src", allow_bf16=True)
     if index.dim() != 1 or index.shape[0] != src.shape[0]:
         raise RuntimeError("hierarchicalgnn_amd.scatter_add: index must be 1-D with one entry per row of src")
@@ -180,6 +187,180 @@ def scatter_add(src: torch.Tensor, index: torch.Tensor, dim: int = 0, dim_size: 
             raise RuntimeError("hierarchicalgnn_amd.scatter_add: weight must have one entry per row")
     res = _ScatterAdd.apply(src2d, weight, plan)
     return res.reshape((dim_size,) + trailing)
+
+
+# --------------------------------------------------------------------------- scatter_min / scatter_max / integer sums
+_INT_DTYPES = (torch.int32, torch.int64)
+_EX_DTYPES = {torch.float32: _lib.DT_F32, torch.bfloat16: _lib.DT_BF16, torch.int32: _lib.DT_I32,
+              torch.int64: _lib.DT_I64}
+
+
+def _norm_dim(dim: int, ndim: int, what: str) -> int:
+    d = int(dim) + ndim if int(dim) < 0 else int(dim)
+    if not 0 <= d < ndim:
+        raise RuntimeError(f"hierarchicalgnn_amd.{what}: dim {dim} out of range for a {ndim}-d src")
+    return d
+
+
+def _seg_ex(plan: GraphPlan, op: int, src2d: torch.Tensor):
+    """hgnn_segment_reduce_ex over a contiguous [M, F] src: (out[N, F], arg[N, F] int64 or None for SUM)"""
+    F = int(src2d.shape[1])
+    out = torch.empty((plan.N, F), dtype=src2d.dtype, device=src2d.device)
+    arg = None if op == _lib.RED_SUM else torch.empty((plan.N, F), dtype=torch.int64, device=src2d.device)
+    if plan.N == 0 or F == 0:
+        return out, arg
+    lib = _lib.load()
+    partial, partial_arg = plan.partial_ex(F, src2d.dtype)
+    with torch.cuda.device(src2d.device):
+        _lib.check(lib.hgnn_segment_reduce_ex(
+            ctypes.byref(plan.c), op, _EX_DTYPES[src2d.dtype], _lib.ptr(src2d), F, _lib.ptr(out), _lib.ptr(arg),
+            _lib.ptr(partial), None if op == _lib.RED_SUM else _lib.ptr(partial_arg),
+            _lib.current_stream(src2d.device)), "hgnn_segment_reduce_ex")
+    return out, arg
+
+
+def _arg_backward(arg: torch.Tensor, grad_out: torch.Tensor, M: int) -> torch.Tensor:
+    """grad_src[arg[d, f], f] = grad_out[d, f], zeros elsewhere"""
+    N, F = int(arg.shape[0]), int(arg.shape[1])
+    grad_src = torch.zeros((M, F), dtype=grad_out.dtype, device=grad_out.device)
+    if M == 0 or F == 0:
+        return grad_src
+    lib = _lib.load()
+    with torch.cuda.device(grad_out.device):
+        _lib.check(lib.hgnn_segment_arg_backward(
+            _lib.ptr(arg), N, F, M, _EX_DTYPES[grad_out.dtype], _lib.ptr(grad_out), _lib.ptr(grad_src),
+            _lib.current_stream(grad_out.device)), "hgnn_segment_arg_backward")
+    return grad_src
+
+
+class _ScatterArgReduce(torch.autograd.Function):
+    """(out, arg)[d] = min / max over {(src[e], e): index[e] = d}; the gradient goes to row arg only"""
+
+    @staticmethod
+    def forward(ctx, src2d, plan: GraphPlan, op: int):
+        out, arg = _seg_ex(plan, op, src2d)
+        ctx.mark_non_differentiable(arg)
+        ctx.save_for_backward(arg)
+        ctx.M = plan.M
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_arg):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        arg, = ctx.saved_tensors
+        return _arg_backward(arg, grad_out.contiguous(), ctx.M), None, None
+
+
+def _scatter_ex(src, index, dim, dim_size, plan, validate, op, what):
+    """shared front end of the hgnn_segment_reduce_ex operators: returns (out, arg) shaped like torch_scatter's"""
+    if src.dtype not in _EX_DTYPES:
+        raise RuntimeError(f"hierarchicalgnn_amd.{what}: unsupported dtype {src.dtype} "
+                           "(float32, bfloat16, int32 and int64 are implemented)")
+    if not src.is_cuda or not index.is_cuda:
+        raise RuntimeError(f"hierarchicalgnn_amd.{what}: src and index must be HIP device tensors "
+                           "(no CPU fallback; build + run on an MI355X)")
+    d = _norm_dim(dim, src.dim(), what)
+    if index.dim() != 1 or index.numel() != src.shape[d]:
+        raise RuntimeError(f"hierarchicalgnn_amd.{what}: index must be 1-D with one entry per element of src "
+                           f"along dim {d} (got index {tuple(index.shape)}, src {tuple(src.shape)})")
+    if index.device != src.device:
+        raise RuntimeError(f"hierarchicalgnn_amd.{what}: index and src are on different devices")
+    if index.dtype != torch.int64:
+        index = index.long()
+    if dim_size is None:
+        dim_size = int(index.max().item()) + 1 if index.numel() else 0
+    dim_size = int(dim_size)   # an int, or a 0-d tensor such as pid.max() + 1
+    if plan is None:
+        plan = get_plan(index, dim_size, validate=validate)
+    elif plan.M != index.numel() or plan.N != dim_size or plan.c.has_gather:
+        raise RuntimeError(f"hierarchicalgnn_amd.{what}: plan does not match index/dim_size")
+    x = src.movedim(d, 0)
+    rest = tuple(x.shape[1:])
+    F = 1
+    for t in rest:
+        F *= int(t)
+    x2 = x.reshape(int(x.shape[0]), F).contiguous()
+    if op == _lib.RED_SUM:
+        out, arg = _seg_ex(plan, op, x2)
+    else:
+        out, arg = _ScatterArgReduce.apply(x2, plan, op)
+    shape = (dim_size,) + rest
+    out = out.reshape(shape).movedim(0, d)
+    arg = None if arg is None else arg.reshape(shape).movedim(0, d)
+    if d != 0:
+        out = out.contiguous()
+        arg = None if arg is None else arg.contiguous()
+    return out, arg
+
+
+def scatter_min(src: torch.Tensor, index: torch.Tensor, dim: int = -1, out=None, dim_size=None,
+                plan: Optional[GraphPlan] = None, validate: bool = True):
+    """torch_scatter.scatter_min (2.0.9): ``(out, arg)`` with ``out[..., d, ...]`` the minimum of the elements of
+    ``src`` whose position along ``dim`` has ``index == d``, and ``arg`` (int64) that position.
+
+    ``index`` is 1-D (one entry per position along ``dim``) and broadcast along every other dimension.
+    ``dim_size`` is an int or a 0-d tensor; ``None`` means ``index.max() + 1``.
+    dtypes: float32, bfloat16, int32, int64 (values compared exactly in their own type).
+    Ties: the first occurrence (smallest position) wins, as in torch_scatter's CPU kernel, independent of the
+    plan's chunking (``plan=``, e.g. ``GraphPlan(index, N, chunk=c)``).
+    NaN is never selected (strict comparisons): a segment holding only NaN counts as empty.  +-inf are ordinary
+    values.  Empty segments: ``out = 0`` and ``arg = src.size(dim)``.
+    Differentiable w.r.t. floating-point ``src``: the gradient of ``out[d, f]`` goes to ``src[arg[d, f], f]``
+    only; empty segments contribute nothing.  ``out=`` (accumulation into a given tensor) is not supported and
+    raises.  HIP device tensors only (no CPU fallback)."""
+    if out is not None:
+        raise RuntimeError("hierarchicalgnn_amd.scatter_min: `out=` is not supported")
+    return _scatter_ex(src, index, dim, dim_size, plan, validate, _lib.RED_MIN, "scatter_min")
+
+
+def scatter_max(src: torch.Tensor, index: torch.Tensor, dim: int = -1, out=None, dim_size=None,
+                plan: Optional[GraphPlan] = None, validate: bool = True):
+    """torch_scatter.scatter_max (2.0.9): as :func:`scatter_min` with the maximum (same tie, NaN, +-inf,
+    empty-segment, gradient and ``out=`` rules)."""
+    if out is not None:
+        raise RuntimeError("hierarchicalgnn_amd.scatter_max: `out=` is not supported")
+    return _scatter_ex(src, index, dim, dim_size, plan, validate, _lib.RED_MAX, "scatter_max")
+
+
+def scatter_mean(src: torch.Tensor, index: torch.Tensor, dim: int = 0, out=None, dim_size=None,
+                 plan: Optional[GraphPlan] = None, validate: bool = True) -> torch.Tensor:
+    """torch_scatter.scatter_mean: the sum over the count (empty segments count 1); integer src is floored,
+    as torch_scatter does.  Floating-point src: scatter_add of src and of a column of ones."""
+    if out is not None:
+        raise RuntimeError("hierarchicalgnn_amd.scatter_mean: `out=` is not supported")
+    d = _norm_dim(dim, src.dim(), "scatter_mean")
+    if dim_size is None:
+        dim_size = int(index.max().item()) + 1 if index.numel() else 0
+    dim_size = int(dim_size)
+    if d != 0:
+        return scatter_mean(src.movedim(d, 0), index, 0, None, dim_size, plan, validate).movedim(0, d)
+    total = scatter_add(src, index, dim=0, dim_size=dim_size, plan=plan, validate=validate)
+    view = (-1,) + (1,) * (src.dim() - 1)
+    if src.dtype in _INT_DTYPES:
+        ones = torch.ones(src.shape[0], dtype=src.dtype, device=src.device)
+        count = scatter_add(ones, index, dim=0, dim_size=dim_size, plan=plan, validate=validate).clamp_(min=1)
+        return total.div(count.view(view), rounding_mode="floor")
+    ones = torch.ones(src.shape[0], 1, dtype=src.dtype, device=src.device)
+    count = scatter_add(ones, index, dim=0, dim_size=dim_size).clamp_(min=1)
+    return total / count.view(view)
+
+
+_REDUCE_OPS = ("sum", "add", "mean", "min", "max")
+
+
+def scatter(src: torch.Tensor, index: torch.Tensor, dim: int = -1, out=None, dim_size=None,
+            reduce: str = "sum") -> torch.Tensor:
+    """torch_scatter.scatter: ``reduce`` in sum / add / mean / min / max; min and max return the values only."""
+    if reduce in ("sum", "add"):
+        return scatter_add(src, index, dim=dim, dim_size=dim_size, out=out)
+    if reduce == "mean":
+        return scatter_mean(src, index, dim=dim, out=out, dim_size=dim_size)
+    if reduce == "min":
+        return scatter_min(src, index, dim=dim, out=out, dim_size=dim_size)[0]
+    if reduce == "max":
+        return scatter_max(src, index, dim=dim, out=out, dim_size=dim_size)[0]
+    raise ValueError(f"hierarchicalgnn_amd.scatter: reduce must be one of {_REDUCE_OPS}, got {reduce!r}")
 
 
 # --------------------------------------------------------------------------- K2 / K3 / K5

@@ -117,6 +117,17 @@ class GraphPlan:
             self._partial[F] = buf
         return buf
 
+    # scratch of hgnn_segment_reduce_ex: partial values of `dtype` and int32 partial positions, per (width, dtype)
+    def partial_ex(self, F: int, dtype: torch.dtype):
+        key = (F, dtype)
+        buf = self._partial.get(key)
+        if buf is None:
+            n = max(self.max_partial, 1) * F
+            buf = (torch.empty(n, dtype=dtype, device=self.device),
+                   torch.empty(n, dtype=torch.int32, device=self.device))
+            self._partial[key] = buf
+        return buf
+
     def counts_host(self):
         c = self.counts.cpu().tolist()
         return dict(work=c[_lib.CNT_WORK], split=c[_lib.CNT_SPLIT], partial=c[_lib.CNT_PARTIAL],

@@ -50,7 +50,7 @@ extern "C" {
 #define HGNN_ERR_WORKSPACE 3
 #define HGNN_ERR_UNSUPPORTED 4
 
-#define HGNN_ABI_VERSION 23
+#define HGNN_ABI_VERSION 24
 
 typedef void* hgnn_stream_t; /* hipStream_t */
 
@@ -144,6 +144,38 @@ int hgnn_plan_build(const int64_t* dst_index, const int64_t* gather_index, hgnn_
 int hgnn_segment_reduce_f32(const hgnn_plan* plan, const float* src, int32_t F,
                             const float* weight, const float* row_scale,
                             float* out, float* partial, hgnn_stream_t stream);
+
+/* Segmented min / max with arg output, and exact integer sums, over a plain destination plan (no gather index):
+ * torch_scatter.scatter_min / scatter_max (BipartiteClassification/bipartite_classification_base.py:158,
+ * gMRT/gmrt_base.py:165, tracking_utils.py:41) and the integer scatter_sum of tracking_utils.py:37.
+ *   op     HGNN_RED_MIN / HGNN_RED_MAX: out[d,f] = the min / max of src[e,f] over the rows e of list d,
+ *          arg[d,f] (int64) = that row e.  Ties go to the smallest e (first occurrence); NaN is never
+ *          selected (a list holding only NaN is empty); +-inf are ordinary values.  Empty lists: out = 0,
+ *          arg = n_rows.  Values are compared exactly in their own type (bf16 without rounding, int64 as
+ *          64-bit integers); the result does not depend on the plan's chunk.
+ *          HGNN_RED_SUM (dtype I32 / I64 only; arg unused, may be NULL): out[d,f] = the wrapping integer sum.
+ *          Floating-point sums are hgnn_segment_reduce_f32 / _bf16 (HGNN_ERR_UNSUPPORTED here).
+ *   dtype  HGNN_DT_F32 / _BF16 / _I32 / _I64: the element type of src, out and partial.
+ *   src    [n_rows, F], out [n_dst, F] (every element written), arg int64 [n_dst, F];
+ *   partial      scratch of plan->max_partial * F elements of dtype,
+ *   partial_arg  int32 scratch of plan->max_partial * F elements (MIN / MAX only; NULL for SUM).
+ * Rows of 4-element columns (F % 4 == 0, F <= 1024, 16-byte aligned pointers; 8-byte for bf16) take the
+ * vector path, any other shape a row-parallel path.  Deterministic: no atomics, each element written once. */
+#define HGNN_RED_SUM 0
+#define HGNN_RED_MIN 1
+#define HGNN_RED_MAX 2
+#define HGNN_DT_F32 0
+#define HGNN_DT_BF16 1
+#define HGNN_DT_I32 2
+#define HGNN_DT_I64 3
+int hgnn_segment_reduce_ex(const hgnn_plan* plan, int32_t op, int32_t dtype, const void* src, int32_t F,
+                           void* out, int64_t* arg, void* partial, int32_t* partial_arg, hgnn_stream_t stream);
+
+/* Backward of the min / max above: grad_src[arg[d,f], f] = grad_out[d,f] where 0 <= arg[d,f] < n_rows, and 0
+ * everywhere else (grad_src [n_rows, F] is cleared first).  Each element receives at most one value: no atomics.
+ * dtype HGNN_DT_F32 or HGNN_DT_BF16 (integer src is not differentiable). */
+int hgnn_segment_arg_backward(const int64_t* arg, int64_t n_dst, int32_t F, int64_t n_rows, int32_t dtype,
+                              const void* grad_out, void* grad_src, hgnn_stream_t stream);
 
 /* out[e,:] = weight[e] * row_scale[idx[e]] * table[idx[e],:]   (idx[e] < 0 -> zeros)
  * idx: int32[M]; weight float[M] / row_scale float[table_rows] may be NULL. */

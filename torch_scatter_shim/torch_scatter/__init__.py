@@ -1,15 +1,28 @@
 """``torch_scatter`` import shim: put ``<repo>/torch_scatter_shim`` on PYTHONPATH and the
-reference's ``from torch_scatter import scatter_add`` (Modules/gnn_utils.py:5,
-BipartiteClassification/Models/HGNN_GMM.py:5) resolves to the MI355X HIP kernel.
+reference's ``from torch_scatter import ...`` (Modules/gnn_utils.py:5,
+BipartiteClassification/Models/HGNN_GMM.py:5, bipartite_classification_base.py,
+gmrt_base.py, tracking_utils.py) resolves to the MI355X HIP kernels.
 
-Only the call shape on the hot path is accelerated (``scatter_add`` with a 1-D index,
-``dim=0``).  ``scatter_mean`` (HGNN_GMM.py:251, centroids of 8-wide embeddings) is
-expressed through the same kernel.  ``scatter_min/max`` are evaluation-only in the
-reference (tracking_utils.py) and are not provided.
+Provided (torch_scatter 2.0.9 semantics, HIP device tensors only, no CPU fallback):
+
+- ``scatter_add`` / ``scatter_sum``: float32 / bfloat16 through the message-passing
+  kernel (K1); int32 / int64 give an exact integer sum (tracking_utils.py:37).
+- ``scatter_mean``: the sum over the count; integer src is floored (HGNN_GMM.py:251).
+- ``scatter_min`` / ``scatter_max`` -> ``(out, arg)`` (the BC / gMRT training loss,
+  bipartite_classification_base.py:158, and the evaluation, tracking_utils.py:41).
+  float32, bfloat16, int32, int64; ``dim`` defaults to -1 as in torch_scatter.
+  Ties: the first occurrence along ``dim`` wins (deterministic).  NaN is never
+  selected; a segment holding only NaN is empty.  Empty segments: out = 0,
+  arg = src.size(dim).  The gradient goes to the ``arg`` position only.
+- ``scatter(..., reduce=)`` with reduce in sum / add / mean / min / max (min / max
+  return the values only).
+
+Not supported: ``out=`` (raises), an index with more than one dimension, other dtypes
+(raise ``RuntimeError`` naming the dtype), ``scatter_mul`` / ``scatter_std`` /
+``scatter_logsumexp`` / ``segment_*``.
 """
-import torch
-
-from hierarchicalgnn_amd.ops import scatter_add  # noqa: F401
+from hierarchicalgnn_amd import ops as _ops
+from hierarchicalgnn_amd.ops import scatter, scatter_add, scatter_max, scatter_min  # noqa: F401
 
 
 def scatter_sum(src, index, dim=0, out=None, dim_size=None):
@@ -17,17 +30,4 @@ def scatter_sum(src, index, dim=0, out=None, dim_size=None):
 
 
 def scatter_mean(src, index, dim=0, out=None, dim_size=None):
-    if dim_size is None:
-        dim_size = int(index.max().item()) + 1 if index.numel() else 0
-    total = scatter_add(src, index, dim=dim, dim_size=dim_size, out=out)
-    ones = torch.ones(src.shape[0], 1, dtype=src.dtype, device=src.device)
-    count = scatter_add(ones, index, dim=0, dim_size=dim_size).clamp_(min=1)
-    return total / count.view(-1, *([1] * (src.dim() - 1)))
-
-
-def _unsupported(*a, **k):
-    raise NotImplementedError("torch_scatter shim (hierarchicalgnn_amd): only scatter_add/scatter_sum/"
-                              "scatter_mean are provided; scatter_min/max are evaluation-side in the reference")
-
-
-scatter_min = scatter_max = _unsupported
+    return _ops.scatter_mean(src, index, dim=dim, out=out, dim_size=dim_size)
