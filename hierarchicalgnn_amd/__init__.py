@@ -6,6 +6,7 @@ Drop-in surface (same names / signatures as the reference):
     scatter_min / scatter_max / scatter_mean / scatter   <- torch_scatter (same names)
     InteractionGNNCell(hparams), HierarchicalGNNCell(hparams)   <- Modules/gnn_utils.py
     make_mlp(...)                                        <- Modules/utils.py
+    eval_metrics(bipartite_graph, event, ...)            <- Modules/tracking_utils.py
 
 Everything on the hot path runs in hand-written HIP kernels loaded from
 libhgnn_hip.so through the C ABI of include/hgnn_hip.h; there is no CPU or
@@ -16,5 +17,6 @@ from .ops import scatter, scatter_max, scatter_mean, scatter_min  # noqa: F401
 from .plan import GraphPlan, get_plan, clear_plan_cache, plan_cache_stats  # noqa: F401
 from .utils import make_mlp  # noqa: F401
 from .gnn_utils import InteractionGNNCell, HierarchicalGNNCell  # noqa: F401
+from .tracking import eval_metrics, edge_track_candidates, bipartite_track_candidates  # noqa: F401
 
 __version__ = "0.1.0"

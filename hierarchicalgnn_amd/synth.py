@@ -98,3 +98,56 @@ def degree_stats(index: torch.Tensor, n: int):
     deg = torch.bincount(index, minlength=n)
     return dict(mean=float(deg.float().mean()), max=int(deg.max()), median=float(deg.float().median()),
                 zero=int((deg == 0).sum()))
+
+
+def tracking_event(n_hits: int = 120_000, hits_per_particle: int = 10, noise_fraction: float = 0.1,
+                   primary_fraction: float = 0.9, seed: int = 1234):
+    """TrackML-shaped truth for the tracking metrics (reference tracking_utils.eval_metrics): returns a dict
+    {pid int64[N] (0 = noise, the rest large distinct ids), pt float32[N] (GeV, per particle with a small per-hit
+    spread; 0 on noise, as the training bases set it), primary int64[N] (per particle)} on the CPU"""
+    g = torch.Generator().manual_seed(seed + 13)
+    n_noise = int(round(n_hits * noise_fraction))
+    n_sig = n_hits - n_noise
+    n_part = max(1, n_sig // hits_per_particle)
+    part = torch.randint(0, n_part, (n_sig,), generator=g)          # ~Poisson(hits_per_particle) hits per particle
+    ids = ((torch.randperm(n_part, generator=g) + 1) << 20) | torch.randint(0, 1 << 20, (n_part,), generator=g)
+    pt_p = 0.2 - torch.log(torch.rand(n_part, generator=g).clamp_(min=1e-12))
+    prim_p = (torch.rand(n_part, generator=g) < primary_fraction).long()
+    pid = torch.cat([ids[part], torch.zeros(n_noise, dtype=torch.long)])
+    pt = torch.cat([pt_p[part] * (1 + 0.02 * torch.rand(n_sig, generator=g)), torch.zeros(n_noise)]).float()
+    primary = torch.cat([prim_p[part], torch.zeros(n_noise, dtype=torch.long)])
+    perm = torch.randperm(n_hits, generator=g)
+    return {"pid": pid[perm].contiguous(), "pt": pt[perm].contiguous(), "primary": primary[perm].contiguous()}
+
+
+def track_candidates(pid: torch.Tensor, n_pairs: int = 600_000, n_candidates: int = 10_000,
+                     clean_fraction: float = 0.8, hit_loss: float = 0.1, seed: int = 1234) -> torch.Tensor:
+    """a hit -> track-candidate bipartite graph int64[2, ~n_pairs] for the event truth `pid`: clean candidates
+    (a seed particle's hits, each lost with `hit_loss`, plus ~2 foreign hits; a particle may seed two) and large
+    junk candidates that take the rest of the pair budget as random hits.  Labels are arbitrary vertex-like ids."""
+    g = torch.Generator().manual_seed(seed + 17)
+    n = pid.numel()
+    uniq, q = torch.unique(pid, return_inverse=True)
+    sig = torch.nonzero(pid != 0).reshape(-1)
+    signal = torch.nonzero(uniq != 0).reshape(-1)
+    n_clean = int(n_candidates * clean_fraction)
+    seed_p = signal[torch.randint(0, signal.numel(), (n_clean,), generator=g)]
+    cnt = torch.bincount(seed_p, minlength=uniq.numel())
+    order = torch.argsort(seed_p, stable=True)
+    off = torch.cumsum(cnt, 0) - cnt
+    reps = cnt[q[sig]]
+    h = torch.repeat_interleave(sig, reps)
+    k = torch.arange(h.numel()) - torch.repeat_interleave(torch.cumsum(reps, 0) - reps, reps)
+    c = order[off[q[h]] + k]
+    keep = torch.rand(h.numel(), generator=g) >= hit_loss
+    h, c = h[keep], c[keep]
+    n_extra = 2 * n_clean
+    h = torch.cat([h, torch.randint(0, n, (n_extra,), generator=g)])
+    c = torch.cat([c, torch.randint(0, n_clean, (n_extra,), generator=g)])
+    rest = n_pairs - h.numel()
+    if rest > 0 and n_candidates > n_clean:
+        h = torch.cat([h, torch.randint(0, n, (rest,), generator=g)])
+        c = torch.cat([c, torch.randint(n_clean, n_candidates, (rest,), generator=g)])
+    labels = torch.randperm(max(n, n_candidates), generator=g)[:n_candidates]
+    perm = torch.randperm(h.numel(), generator=g)
+    return torch.stack([h[perm], labels[c[perm]]]).contiguous()

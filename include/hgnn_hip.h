@@ -50,7 +50,7 @@ extern "C" {
 #define HGNN_ERR_WORKSPACE 3
 #define HGNN_ERR_UNSUPPORTED 4
 
-#define HGNN_ABI_VERSION 24
+#define HGNN_ABI_VERSION 25
 
 typedef void* hgnn_stream_t; /* hipStream_t */
 
@@ -449,6 +449,39 @@ int hgnn_mlp_backward_layer_supported_bf16(int32_t K, int32_t N);
 int hgnn_mlp_backward_layer_bf16(const void* dz, int64_t M, int32_t K, int32_t N, const void* Wt_frag,
                                  const void* z_prev, const float* ln_w, const float* ln_b, int32_t act, float eps,
                                  const void* skip, void* out, void* a_prev, float* partials, hgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Tracking-performance metrics (reference Modules/tracking_utils.py:18-83, eval_metrics, cupy / cupy.sparse
+ * there; the validation and test steps of every training base end in it).  ABI 25.
+ *
+ * hgnn_track_eval: pairs (hit[b], cand[b]), b < n_pairs, assign hits to track candidates (int64 labels, any
+ *   values); the event's truth is pid[n_hits] (int64, 0 = noise), pt[n_hits] (float32) and, or NULL,
+ *   primary[n_hits] (uint8, != 0 = primary; NULL = primary=False in the reference).  Candidates with
+ *   float(count) < float(nhits_cut * majority_cut) pairs are dropped, the rest relabelled densely; particles are
+ *   the distinct pids.  The matching, its filter and the four metrics follow the reference exactly (DESIGN.md
+ *   section 3, "Tracking metrics").  majority_cut > 0.  result: device double[HGNN_TE_RESULT] (indices below).
+ *   A hit id outside [0, n_hits) does not fault: result[HGNN_TE_STATUS] = 1 and the other entries are
+ *   meaningless.  No match before or after the filter (also: no pair survives the size filter) gives
+ *   result[HGNN_TE_NO_MATCH] = 1, the reference's default_response.  Deterministic: two calls give the same bits.
+ * hgnn_track_eval_workspace_bytes: device scratch of one call (any 256-B aligned).
+ * ------------------------------------------------------------------------ */
+#define HGNN_TE_TRACK_EFF 0
+#define HGNN_TE_TRACK_PUR 1
+#define HGNN_TE_HIT_EFF 2
+#define HGNN_TE_HIT_PUR 3
+#define HGNN_TE_N_KEPT 4    /* matches kept by the filter (n > majority_cut * nhits_cut, pid != 0) */
+#define HGNN_TE_N_MASK 5    /* kept matches of reconstructable particles                           */
+#define HGNN_TE_N_TRUTH 6   /* reconstructable particles                                           */
+#define HGNN_TE_N_CAND 7    /* C: candidates after the size filter                                 */
+#define HGNN_TE_N_PART 8    /* P: distinct pids                                                    */
+#define HGNN_TE_NO_MATCH 9  /* 1: default_response                                                 */
+#define HGNN_TE_STATUS 10   /* 1: a hit id was out of range                                        */
+#define HGNN_TE_N_MATCH 11  /* matches before the filter                                           */
+#define HGNN_TE_RESULT 12
+int hgnn_track_eval_workspace_bytes(int64_t n_pairs, int64_t n_hits, size_t* bytes);
+int hgnn_track_eval(const int64_t* hit, const int64_t* cand, int64_t n_pairs, const int64_t* pid, const float* pt,
+                    const uint8_t* primary, int64_t n_hits, double pt_cut, double nhits_cut, double majority_cut,
+                    double* result, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
 
 #ifdef __cplusplus
 }
