@@ -7,6 +7,7 @@ Drop-in surface (same names / signatures as the reference):
     InteractionGNNCell(hparams), HierarchicalGNNCell(hparams)   <- Modules/gnn_utils.py
     make_mlp(...)                                        <- Modules/utils.py
     eval_metrics(bipartite_graph, event, ...)            <- Modules/tracking_utils.py
+    graph_intersection(...), frnn_graph(...)             <- Modules/utils.py (embedding stage)
 
 Everything on the hot path runs in hand-written HIP kernels loaded from
 libhgnn_hip.so through the C ABI of include/hgnn_hip.h; there is no CPU or
@@ -18,5 +19,6 @@ from .plan import GraphPlan, get_plan, clear_plan_cache, plan_cache_stats  # noq
 from .utils import make_mlp  # noqa: F401
 from .gnn_utils import InteractionGNNCell, HierarchicalGNNCell  # noqa: F401
 from .tracking import eval_metrics, edge_track_candidates, bipartite_track_candidates  # noqa: F401
+from .embedding import frnn_graph, graph_intersection, training_samples, training_weights, hinge_distance  # noqa: F401
 
 __version__ = "0.1.0"

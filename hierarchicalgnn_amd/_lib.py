@@ -17,12 +17,12 @@ LIB_PATH = os.environ.get("HGNN_LIB") or os.path.join(_HERE, "csrc", "libhgnn_hi
 
 HGNN_OK = 0
 CNT_WORK, CNT_SPLIT, CNT_PARTIAL, CNT_ERR, CNT_VALID, CNT_UNSORTED = 0, 1, 2, 3, 4, 5
-ABI_VERSION = 25
+ABI_VERSION = 26
 MLP_BWD_BLOCKS = 512   # HGNN_MLP_BWD_BLOCKS
 GMM_STATE, GMM_BLOCKS = 16, 1024   # HGNN_GMM_STATE, HGNN_GMM_BLOCKS
 LN_ACT_BLOCKS = 1024   # HGNN_LN_ACT_BLOCKS
 RED_SUM, RED_MIN, RED_MAX = 0, 1, 2   # HGNN_RED_*
-DT_F32, DT_BF16, DT_I32, DT_I64 = 0, 1, 2, 3   # HGNN_DT_*
+DT_F32, DT_BF16, DT_I32, DT_I64, DT_F64 = 0, 1, 2, 3, 4   # HGNN_DT_*
 # HGNN_TE_*: entries of hgnn_track_eval's result vector
 (TE_TRACK_EFF, TE_TRACK_PUR, TE_HIT_EFF, TE_HIT_PUR, TE_N_KEPT, TE_N_MASK, TE_N_TRUTH, TE_N_CAND, TE_N_PART,
  TE_NO_MATCH, TE_STATUS, TE_N_MATCH, TE_RESULT) = range(13)
@@ -124,6 +124,9 @@ _SIGNATURES = {
     "hgnn_track_eval_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
     "hgnn_track_eval": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double,
                                 c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hgnn_graph_intersection_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, POINTER(c_size_t)]),
+    "hgnn_graph_intersection": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

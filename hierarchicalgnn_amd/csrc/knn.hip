@@ -220,23 +220,35 @@ static void launch_knn(const float* query, int64_t nq, const float* points, int6
 
 using namespace hgnn;
 
+// 33 <= K <= 128: knn_large.hip
+void hgnn_knn_large_slices(int64_t nq, int64_t np, int* slices, int64_t* slice_len);
+int hgnn_knn_large_launch(const float* query, int64_t nq, const float* points, int64_t np, int D, int K, float radius,
+                          const float* r_dev, int64_t* idx_out, float* d2_out, void* ws, hipStream_t stream);
+
+static size_t knn_ws_bytes(int64_t nq, int64_t np, int32_t K) {
+    int slices;
+    int64_t slice_len;
+    if (K > 32) hgnn_knn_large_slices(nq, np, &slices, &slice_len);
+    else knn_slices(nq, np, &slices, &slice_len);
+    return slices > 1 ? (size_t)nq * slices * K * 8 : 0;
+}
+
 static int knn_dispatch(const float* query, int64_t nq, const float* points, int64_t np, int32_t D, int32_t K,
                         float radius, const float* r_dev, int64_t* idx_out, float* dist2_out, void* ws,
                         size_t ws_bytes, hipStream_t stream, const char* who) {
     HGNN_REQUIRE(nq >= 0 && np >= 0 && np < ((int64_t)1 << 31), "%s: bad sizes", who);
     HGNN_REQUIRE(D >= 1 && D <= kKnnDMax, "%s: D must be in [1, %d] (got %d)", who, kKnnDMax, D);
-    HGNN_REQUIRE(K >= 1 && K <= 32, "%s: K must be in [1, 32] (got %d)", who, K);
+    HGNN_REQUIRE(K >= 1 && K <= 128, "%s: K must be in [1, 128] (got %d)", who, K);
     HGNN_REQUIRE(r_dev != nullptr || radius >= 0.f, "%s: negative radius", who);
     if (nq == 0) return HGNN_OK;
     HGNN_REQUIRE(query != nullptr && idx_out != nullptr && (np == 0 || points != nullptr), "%s: NULL pointer", who);
     if (ws != nullptr) {
-        int slices;
-        int64_t slice_len;
-        knn_slices(nq, np, &slices, &slice_len);
-        const size_t need = slices > 1 ? (size_t)nq * slices * K * 8 : 0;
+        const size_t need = knn_ws_bytes(nq, np, K);
         HGNN_REQUIRE(ws_bytes >= need && (uintptr_t)ws % 16 == 0, "%s: workspace too small (%zu < %zu) or unaligned",
                      who, ws_bytes, need);
     }
+    if (K > 32)
+        return hgnn_knn_large_launch(query, nq, points, np, D, K, radius, r_dev, idx_out, dist2_out, ws, stream);
 #define HGNN_KNN(KK) launch_knn<KK>(query, nq, points, np, D, radius, r_dev, idx_out, dist2_out, ws, stream)
     switch (K) {
         case 1: HGNN_KNN(1); break;
@@ -268,11 +280,9 @@ extern "C" int hgnn_knn_radius_f32(const float* query, int64_t nq, const float* 
 }
 
 extern "C" int hgnn_knn_workspace_bytes(int64_t nq, int64_t np, int32_t K, size_t* bytes) {
-    HGNN_REQUIRE(bytes != nullptr && nq >= 0 && np >= 0 && K >= 1 && K <= 32, "hgnn_knn_workspace_bytes: bad argument");
-    int slices;
-    int64_t slice_len;
-    knn_slices(nq, np, &slices, &slice_len);
-    *bytes = slices > 1 ? (size_t)nq * slices * K * 8 : 0;
+    HGNN_REQUIRE(bytes != nullptr && nq >= 0 && np >= 0, "hgnn_knn_workspace_bytes: bad argument");
+    HGNN_REQUIRE(K >= 1 && K <= 128, "hgnn_knn_workspace_bytes: K must be in [1, 128] (got %d)", K);
+    *bytes = knn_ws_bytes(nq, np, K);
     return HGNN_OK;
 }
 

@@ -5,6 +5,7 @@ for a plain training loop).
 
     InteractionGNNBlock  <- EdgeClassifier/Models/IN.py:15-95
     EC_InteractionGNN    <- EdgeClassifier/Models/IN.py:97-128
+    Embedding_InteractionGNN <- GNNEmbedding/Models/IN.py:99-118
 
 Sub-module names (``ignn_block.node_encoder``, ``ignn_block.edge_encoder``,
 ``ignn_block.ignn_cells.{i}``, ``edge_classifier``) and therefore the
@@ -156,6 +157,25 @@ class EC_InteractionGNN(nn.Module):
         # IN.py:126 -- relies on the ORIGINAL edge order: edges[:E] pairs with edges[E:]
         scores = concat_mlp(self.edge_classifier, [(edges[:e], None), (edges[e:], None)]).squeeze(-1)
         return torch.sigmoid(scores.float())
+
+
+class Embedding_InteractionGNN(nn.Module):
+    """GNNEmbedding/Models/IN.py:99-118 without its Lightning base: forward(x[N,3], graph[2,E]) -> unit
+    embeddings[N, emb_dim] of the doubled graph.  The pair construction of its training step is
+    hierarchicalgnn_amd.embedding."""
+
+    def __init__(self, hparams):
+        super().__init__()
+        hparams = process_hparams(hparams)
+        self.hparams = hparams
+        self.ignn_block = InteractionGNNBlock(hparams, hparams["n_interaction_graph_iters"], emb=True)
+        _mark_split3(self, hparams)
+
+    def forward(self, x, graph):
+        graph = stable_index(graph)
+        directed_graph = memo(graph, "directed", lambda: torch.cat([graph, graph.flip(0)], dim=1))  # IN.py:114
+        embeddings, _, _ = self.ignn_block(x, directed_graph)
+        return embeddings
 
 
 class HierarchicalGNNBlock(nn.Module):

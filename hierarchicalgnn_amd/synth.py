@@ -151,3 +151,33 @@ def track_candidates(pid: torch.Tensor, n_pairs: int = 600_000, n_candidates: in
     labels = torch.randperm(max(n, n_candidates), generator=g)[:n_candidates]
     perm = torch.randperm(h.numel(), generator=g)
     return torch.stack([h[perm], labels[c[perm]]]).contiguous()
+
+
+def embedding_event(n_hits: int = 120_000, emb_dim: int = 8, hits_per_particle: int = 10, spread: float = 0.1,
+                    noise_fraction: float = 0.1, seed: int = 1234):
+    """An event for the embedding stage's pair construction (GNNEmbedding/embedding_base.py:109-146): returns a
+    dict of CPU tensors {embeddings float32 [N, emb_dim] unit vectors clustered by particle (centre + spread * noise,
+    normalised; noise hits uniform on the sphere), pid int64 [N] (0 = noise), pt float32 [N] (GeV; 0 on noise),
+    signal_mask bool [N] (~95 % true), modulewise_true_edges int64 [2, E] (consecutive hits of every particle)}"""
+    g = torch.Generator().manual_seed(seed + 19)
+    n_noise = int(round(n_hits * noise_fraction))
+    n_sig = n_hits - n_noise
+    n_part = max(1, n_sig // hits_per_particle)
+    part = torch.randint(0, n_part, (n_sig,), generator=g)
+    centres = torch.nn.functional.normalize(torch.randn(n_part, emb_dim, generator=g), dim=1)
+    sig = torch.nn.functional.normalize(centres[part] + spread * torch.randn(n_sig, emb_dim, generator=g), dim=1)
+    noise = torch.nn.functional.normalize(torch.randn(n_noise, emb_dim, generator=g), dim=1)
+    pt_p = 0.2 - torch.log(torch.rand(n_part, generator=g).clamp_(min=1e-12))
+    emb = torch.cat([sig, noise])
+    pid = torch.cat([part + 1, torch.zeros(n_noise, dtype=torch.long)])
+    pt = torch.cat([pt_p[part], torch.zeros(n_noise)]).float()
+    perm = torch.randperm(n_hits, generator=g)
+    emb, pid, pt = emb[perm].contiguous(), pid[perm].contiguous(), pt[perm].contiguous()
+    signal_mask = torch.rand(n_hits, generator=g) >= 0.05
+    # truth: the hits of every particle in index order, consecutive ones joined
+    order = torch.argsort(pid * n_hits + torch.arange(n_hits), stable=True)
+    p_sorted = pid[order]
+    same = (p_sorted[1:] == p_sorted[:-1]) & (p_sorted[1:] != 0)
+    edges = torch.stack([order[:-1][same], order[1:][same]])
+    return {"embeddings": emb, "pid": pid, "pt": pt, "signal_mask": signal_mask,
+            "modulewise_true_edges": edges.contiguous()}

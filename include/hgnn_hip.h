@@ -50,7 +50,7 @@ extern "C" {
 #define HGNN_ERR_WORKSPACE 3
 #define HGNN_ERR_UNSUPPORTED 4
 
-#define HGNN_ABI_VERSION 25
+#define HGNN_ABI_VERSION 26
 
 typedef void* hgnn_stream_t; /* hipStream_t */
 
@@ -168,6 +168,7 @@ int hgnn_segment_reduce_f32(const hgnn_plan* plan, const float* src, int32_t F,
 #define HGNN_DT_BF16 1
 #define HGNN_DT_I32 2
 #define HGNN_DT_I64 3
+#define HGNN_DT_F64 4   /* hgnn_graph_intersection weights only (ABI 26) */
 int hgnn_segment_reduce_ex(const hgnn_plan* plan, int32_t op, int32_t dtype, const void* src, int32_t F,
                            void* out, int64_t* arg, void* partial, int32_t* partial_arg, hgnn_stream_t stream);
 
@@ -218,7 +219,10 @@ int hgnn_index_to_i32(const int64_t* idx, int64_t M, int64_t limit, int32_t* out
  * the <=K nearest points with squared distance < radius^2, ascending (ties: lower index first),
  * idx -1 padded; dist2_out (may be NULL) holds squared distances, -1 for padding.
  * Replaces frnn.frnn_grid_points as called by find_neighbors (Modules/utils.py:228-239) from
- * DynamicGraphConstruction.forward (Modules/gnn_utils.py:194).  K in {1-6,8,10,12,16,20,32}. */
+ * DynamicGraphConstruction.forward (Modules/gnn_utils.py:194).  K in {1-6,8,10,12,16,20,32} or any K in
+ * [33, 128] (ABI 26; the embedding stage's FRNN_graph, knn: 100).  Exactly: the K smallest (d2, idx) pairs in
+ * lexicographic order among the points with d2 < radius^2 (radius^2 rounded in float32), so a K = 64 call's first
+ * 32 columns equal a K = 32 call bit for bit.  This entry accepts K > 32 too (one pass, no candidate split). */
 int hgnn_knn_radius_f32(const float* query, int64_t nq, const float* points, int64_t np, int32_t D,
                         int32_t K, float radius, int64_t* idx_out, float* dist2_out, hgnn_stream_t stream);
 
@@ -482,6 +486,25 @@ int hgnn_track_eval_workspace_bytes(int64_t n_pairs, int64_t n_hits, size_t* byt
 int hgnn_track_eval(const int64_t* hit, const int64_t* cand, int64_t n_pairs, const int64_t* pid, const float* pt,
                     const uint8_t* primary, int64_t n_hits, double pt_cut, double nhits_cut, double majority_cut,
                     double* result, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * graph_intersection of the embedding stage (reference Modules/utils.py:117-166, scipy CSR there).  ABI 26.
+ *
+ * hgnn_graph_intersection: pred [2, e_pred] and truth [2, e_truth] int64 (rows, then cols), ids in [0, 2^31).
+ *   out_graph [2, e_pred] int64 (row stride e_pred) receives the U distinct pred pairs in row-major order,
+ *   out_y [e_pred] uint8 whether each also occurs in truth; with weights (truth's, float32 or float64 by
+ *   weight_dtype = HGNN_DT_F32 / HGNN_DT_F64; NULL = no weights, out_weights NULL too) out_weights [e_pred] of that
+ *   dtype receives the sum of the weights over the truth copies of each output pair (0 if none), summed in the
+ *   truth order.  out_count_and_status: device int64[2] = {U, status}; status 1 = an id outside [0, 2^31) (nothing
+ *   else is written, never a fault).  Only out[.., :U] is meaningful.  Allocates nothing, never synchronises;
+ *   deterministic.
+ * hgnn_graph_intersection_workspace_bytes: device scratch of one call (any 256-B aligned).
+ * ------------------------------------------------------------------------ */
+int hgnn_graph_intersection_workspace_bytes(int64_t e_pred, int64_t e_truth, int32_t with_weights, size_t* bytes);
+int hgnn_graph_intersection(const int64_t* pred, int64_t e_pred, const int64_t* truth, int64_t e_truth,
+                            const void* weights, int32_t weight_dtype, int64_t* out_graph, uint8_t* out_y,
+                            void* out_weights, int64_t* out_count_and_status, void* workspace,
+                            size_t workspace_bytes, hgnn_stream_t stream);
 
 #ifdef __cplusplus
 }
