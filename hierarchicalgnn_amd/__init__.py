@@ -8,6 +8,7 @@ Drop-in surface (same names / signatures as the reference):
     make_mlp(...)                                        <- Modules/utils.py
     eval_metrics(bipartite_graph, event, ...)            <- Modules/tracking_utils.py
     graph_intersection(...), frnn_graph(...)             <- Modules/utils.py (embedding stage)
+    bipartite_loss(...), bc_training_loss(...)           <- BipartiteClassificationBase.get_bipartite_loss / training_step
 
 Everything on the hot path runs in hand-written HIP kernels loaded from
 libhgnn_hip.so through the C ABI of include/hgnn_hip.h; there is no CPU or
@@ -20,5 +21,7 @@ from .utils import make_mlp  # noqa: F401
 from .gnn_utils import InteractionGNNCell, HierarchicalGNNCell  # noqa: F401
 from .tracking import eval_metrics, edge_track_candidates, bipartite_track_candidates  # noqa: F401
 from .embedding import frnn_graph, graph_intersection, training_samples, training_weights, hinge_distance  # noqa: F401
+from .assignment import (max_weight_matching, bipartite_loss, bc_embedding_loss, bc_training_loss,  # noqa: F401
+                         gap_bound)
 
 __version__ = "0.1.0"

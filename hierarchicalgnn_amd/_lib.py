@@ -27,6 +27,11 @@ DT_F32, DT_BF16, DT_I32, DT_I64, DT_F64 = 0, 1, 2, 3, 4   # HGNN_DT_*
 (TE_TRACK_EFF, TE_TRACK_PUR, TE_HIT_EFF, TE_HIT_PUR, TE_N_KEPT, TE_N_MASK, TE_N_TRUTH, TE_N_CAND, TE_N_PART,
  TE_NO_MATCH, TE_STATUS, TE_N_MATCH, TE_RESULT) = range(13)
 
+# HGNN_AM_*: hgnn_assign_match's constants, status bits and the entries of its info vector
+AM_SCALE_BITS, AM_FALLBACK_WEIGHT = 30, 1e-12
+AM_ST_BAD_ID, AM_ST_BAD_WEIGHT, AM_ST_OVERFLOW, AM_ST_BUDGET = 1, 2, 4, 8
+AM_N_PAIRS, AM_STATUS, AM_PHASES, AM_GRID_ROUNDS, AM_TAIL_ROUNDS, AM_HOST_READS = range(6)
+AM_INFO = 8
 
 class HgnnPlan(Structure):
     """mirror of ``struct hgnn_plan``"""
@@ -127,6 +132,9 @@ _SIGNATURES = {
     "hgnn_graph_intersection_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, POINTER(c_size_t)]),
     "hgnn_graph_intersection": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hgnn_assign_match_workspace_bytes": (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "hgnn_assign_match": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

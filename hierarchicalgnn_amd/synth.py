@@ -181,3 +181,30 @@ def embedding_event(n_hits: int = 120_000, emb_dim: int = 8, hits_per_particle: 
     edges = torch.stack([order[:-1][same], order[1:][same]])
     return {"embeddings": emb, "pid": pid, "pt": pt, "signal_mask": signal_mask,
             "modulewise_true_edges": edges.contiguous()}
+
+
+def assignment_event(n_hits: int = 120_000, n_super: int = 10_000, k: int = 5, seed: int = 1234, dyadic: bool = False):
+    """An event for the assignment loss (BipartiteClassification/bipartite_classification_base.py:152-191): pid and
+    pt from ``tracking_event``, the hit -> cluster graph from ``bipartite_assignment`` with the first edge of every
+    signal hit rewired to its particle's home cluster, and scores in (0, 1] that favour the home cluster (0.5 .. 1
+    there, below 0.6 elsewhere).  ``dyadic``: every score is a multiple of 2^-12 in [2^-12, 1], so that sums of
+    scores are exact in float32 and float64 alike.  Returns a dict of CPU tensors {pid int64 [N], pt float32 [N],
+    bipartite_graph int64 [2, N*k], scores float32 [N*k]}."""
+    ev = tracking_event(n_hits, seed=seed)
+    graph, _ = bipartite_assignment(n_hits, n_super, k, seed=seed)
+    g = torch.Generator().manual_seed(seed + 23)
+    uniq, pidx = torch.unique(ev["pid"], return_inverse=True)
+    home = torch.randint(0, n_super, (uniq.numel(),), generator=g)
+    first = torch.argsort(graph[0], stable=True)[::k]            # every hit has exactly k edges
+    first = first[ev["pid"][graph[0][first]] != 0]
+    col = graph[1].clone()
+    col[first] = home[pidx[graph[0][first]]]
+    u = torch.rand(n_hits * k, generator=g)
+    scores = 0.6 * u
+    scores[first] = 0.5 + 0.5 * u[first]
+    if dyadic:
+        scores = (torch.floor(scores * 4096) + 1).clamp_(1, 4096) / 4096
+    else:
+        scores = scores.clamp_(1e-6, 1 - 1e-6)
+    return {"pid": ev["pid"], "pt": ev["pt"], "bipartite_graph": torch.stack([graph[0], col]).contiguous(),
+            "scores": scores.float().contiguous()}

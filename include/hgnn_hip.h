@@ -50,6 +50,8 @@ extern "C" {
 #define HGNN_ERR_WORKSPACE 3
 #define HGNN_ERR_UNSUPPORTED 4
 
+/* hgnn_assign_match and hgnn_assign_match_workspace_bytes were added without a bump: they are additions, and
+ * no existing entry point, struct or constant changed layout or meaning. */
 #define HGNN_ABI_VERSION 26
 
 typedef void* hgnn_stream_t; /* hipStream_t */
@@ -505,6 +507,45 @@ int hgnn_graph_intersection(const int64_t* pred, int64_t e_pred, const int64_t* 
                             const void* weights, int32_t weight_dtype, int64_t* out_graph, uint8_t* out_y,
                             void* out_weights, int64_t* out_count_and_status, void* workspace,
                             size_t workspace_bytes, hgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Max-weight bipartite matching of the assignment loss (reference BipartiteClassification/
+ * bipartite_classification_base.py:152-191 and gmrt_base.py:159-198; scipy CSR and
+ * min_weight_full_bipartite_matching on the host there).  Added under ABI 26.
+ *
+ * hgnn_assign_match: edges (row[b], col[b], score[b]), b < n_edges, row in [0, n_rows), col in [0, n_cols), score
+ *   float32.  pair_row / pair_col / pair_weight [n_edges] receive the U distinct (row, col) pairs in row-major order
+ *   and, in float64, the sum of each pair's scores in ascending original position.  col_match [n_rows]: every row is
+ *   matched to one real column among its pairs, no column twice, or to its private virtual column n_cols + row
+ *   (weight HGNN_AM_FALLBACK_WEIGHT), so that the total weight is maximal for the weights rint(w * 2^S), S =
+ *   HGNN_AM_SCALE_BITS: at most (n_rows + n_cols) * 2^-S below the optimum of the float64 weights, and exactly
+ *   optimal when every weight is a multiple of 2^-S.  Pairs whose weight rounds to 0 tie with the virtual column.
+ *   Solved by an integer eps-scaled auction on the device (csrc/assign.hip); deterministic.
+ *   info: HOST int64[HGNN_AM_INFO] (indices below).  info[HGNN_AM_STATUS] != 0 (HGNN_AM_ST_* bits): col_match is
+ *   not written; the return value is still HGNN_OK.  Nothing faults on a bad id.
+ *   Unlike the other entry points this one SYNCHRONISES the stream: it reads a few words back once after the
+ *   contraction and once per tail launch, info[HGNN_AM_HOST_READS] <= 48 times in all (it gives up with
+ *   HGNN_AM_ST_BUDGET before it would exceed that), so it cannot be captured into a graph.  It allocates nothing.
+ *   Every device loop has a round budget; there is no grid-wide barrier.
+ * hgnn_assign_match_workspace_bytes: device scratch of one call (any 256-B aligned).
+ * ------------------------------------------------------------------------ */
+#define HGNN_AM_SCALE_BITS 30
+#define HGNN_AM_FALLBACK_WEIGHT 1e-12
+#define HGNN_AM_ST_BAD_ID 1      /* a row or col id out of range                                     */
+#define HGNN_AM_ST_BAD_WEIGHT 2  /* a pair weight is not finite or |rint(w * 2^S)| * (n + 1) > 2^56  */
+#define HGNN_AM_ST_OVERFLOW 4    /* a price left the guarded int64 range                             */
+#define HGNN_AM_ST_BUDGET 8      /* the round / host-read budget ran out                             */
+#define HGNN_AM_N_PAIRS 0
+#define HGNN_AM_STATUS 1
+#define HGNN_AM_PHASES 2
+#define HGNN_AM_GRID_ROUNDS 3    /* rounds run as grid launches (idle ones included) */
+#define HGNN_AM_TAIL_ROUNDS 4    /* rounds run inside the single-workgroup kernel    */
+#define HGNN_AM_HOST_READS 5
+#define HGNN_AM_INFO 8
+int hgnn_assign_match_workspace_bytes(int64_t n_edges, int64_t n_rows, int64_t n_cols, size_t* bytes);
+int hgnn_assign_match(const int64_t* row, const int64_t* col, const float* score, int64_t n_edges, int64_t n_rows,
+                      int64_t n_cols, int64_t* col_match, int64_t* pair_row, int64_t* pair_col, double* pair_weight,
+                      int64_t* info, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
 
 #ifdef __cplusplus
 }
