@@ -1,6 +1,7 @@
 // HBM-bound row kernels of the message-passing path (gfx950, wave64):
 //
 //   k_seg_reduce  : destination-sorted segmented reduce = scatter_add without atomics
+//   k_seg_window  : the same for the headline shape (one 1-KiB row per wave instruction, no weight)
 //                   (K1..K5: Modules/gnn_utils.py:50,124,125,142,143;
 //                    BipartiteClassification/Models/HGNN_GMM.py:269)
 //   k_gather_rows : out[e] = w[e]*rs[idx[e]]*table[idx[e]]   (K6 and scatter_add backward)
@@ -31,8 +32,13 @@ namespace f3 { extern int g_opt_split3_rows128; extern int g_opt_split3_one_wg; 
 static int g_opt_nt_loads = 1;   // non-temporal loads for once-read source rows
 static int g_opt_nt_stores = 0;  // non-temporal stores for gather output
 
-__device__ __forceinline__ f32x4 ld4(const float* p, bool nt) {
-    return nt ? __builtin_nontemporal_load((const f32x4*)p) : *(const f32x4*)p;
+// NT is a template parameter on purpose: written as `nt ? nontemporal_load(p) : *p` with a function argument,
+// both arms load the same address, the helper is optimised before it is inlined, and the two loads are merged
+// into one that keeps only the metadata they share, so the hint never reaches a caller.
+template <bool NT>
+__device__ __forceinline__ f32x4 ld4(const void* p) {
+    if constexpr (NT) return __builtin_nontemporal_load((const f32x4*)p);
+    else return *(const f32x4*)p;
 }
 
 // TAG distinguishes the main pass (0), the partial-sum combine pass (1) and the main pass on a
@@ -100,7 +106,7 @@ __global__ __launch_bounds__(WPB * 64) void k_seg_reduce(
                 for (int v = 0; v < VPL; ++v) {
                     const int cv = c + v * 64;
                     if (ok && cv < nvec)
-                        val[u][v] = ld4(rp + cv * 4, NT);
+                        val[u][v] = ld4<NT>(rp + cv * 4);
                     else
                         val[u][v] = f32x4{0.f, 0.f, 0.f, 0.f};
                 }
@@ -138,6 +144,98 @@ __global__ __launch_bounds__(WPB * 64) void k_seg_reduce(
             if (cv < nvec) *(f32x4*)(op + cv * 4) = acc[v];
         }
     }
+}
+
+// The headline shape (one 1-KiB row per wave instruction, no weight, no row scale): a rolling window of W row
+// loads per wave.  After the prologue the oldest row is added and the load of row i+W is issued into the slot it
+// frees, so inside the steady loop (lists of 2W rows and more) the wave waits with a counted vmcnt(W-1).
+// Everything that decides control flow is wave-uniform (the work item comes in by scalar loads, read before the
+// item count is known), so no load sits behind an exec-mask branch.  A ragged end is issued as groups of W/2,
+// W/4, .. 1 rows into slots the drain has added.  That part is NOT overlapped in the main pass as compiled: the
+// conditional overwrite of the last slots makes the compiler copy them first, so a list of W+1..2W-1 rows waits
+// for W-1 of its W loads before its first ragged load goes out (two memory latencies, as in k_seg_reduce); the
+// sorted-layout and combine instantiations drain with vmcnt(W-1), W-2, ..  
+// Rows are added one by one in list order, starting from 0: the sum is bitwise the one of k_seg_reduce.
+// TAG 0 reads its rows through src_row; TAG 1 (combine) and TAG 2 (sorted layout) read rows begin..end-1.
+// Reads before the count is known: wi_begin, wi_end and wi_target need max_items entries each; in the combine
+// pass wi_end is split_pbegin + 1, so split_pbegin needs max_split + 1 entries (include/hgnn_hip.h, hgnn_plan).
+template <int W, bool NT, int TAG, int WPB>
+__global__ __launch_bounds__(WPB * 64) void k_seg_window(
+    const float* __restrict__ src, int F, int nvec, const int32_t* __restrict__ src_row,
+    const int32_t* __restrict__ wi_begin, const int32_t* __restrict__ wi_end,
+    const int32_t* __restrict__ wi_target, const int32_t* __restrict__ n_items_ptr, int64_t max_items,
+    float* __restrict__ out, float* __restrict__ partial) {
+    static_assert(W >= 2 && 64 % W == 0, "a 64-row trip is a whole number of windows");
+    constexpr bool IDENT = TAG != 0;
+    const int lane = threadIdx.x & 63;
+    const int64_t item =
+        (int64_t)blockIdx.x * WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (item >= max_items) return;
+    // four scalar loads issued together: an item past the count (known only now) becomes an empty list that
+    // stores nothing, so that none of the loads can be moved behind a branch on the count
+    const bool valid = item < *n_items_ptr;
+    const int begin = wi_begin[item];
+    const int end = begin + (int)(((uint32_t)wi_end[item] - (uint32_t)begin) & (valid ? ~0u : 0u));
+    const int target = wi_target[item];
+    // lanes past the row's last float4 (F < 256) re-read column 0 and store nothing
+    const uint32_t voff = (uint32_t)(lane < nvec ? lane : 0) * 16u;
+    const size_t row_bytes = (size_t)F * sizeof(float);
+
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 ring[W];
+    int ids = 0, ids_next = 0;
+    if (!IDENT && begin < end) ids_next = src_row[min(begin + lane, end - 1)];
+    for (int base = begin; base < end; base += 64) {
+        const int n = min(end - base, 64);
+        if (!IDENT) {
+            // the next trip's row ids are on their way while this trip's rows stream
+            ids = ids_next;
+            if (base + 64 < end) ids_next = src_row[min(base + 64 + lane, end - 1)];
+        }
+        auto row = [&](int j) -> f32x4 {  // j: wave-uniform position in this trip
+            const uint32_t r = IDENT ? (uint32_t)(base + j) : (uint32_t)__builtin_amdgcn_readlane(ids, j);
+            return ld4<NT>((const char*)src + (size_t)r * row_bytes + voff);
+        };
+        const int full = n & ~(W - 1), rem = n & (W - 1);
+        const bool have = full > 0;  // a list shorter than W goes straight to its ragged end
+        if (have) {
+#pragma unroll
+            for (int u = 0; u < W; ++u) ring[u] = row(u);
+        }
+        for (int j = W; j < full; j += W) {
+#pragma unroll
+            for (int u = 0; u < W; ++u) {
+                acc += ring[u];
+                ring[u] = row(j + u);
+                __builtin_amdgcn_sched_barrier(0);  // keep add-oldest-then-issue order: the wait stays vmcnt(W-1)
+            }
+        }
+        // drain the last whole window; each group of the ragged end goes into slots already added
+        int j = full;
+#pragma unroll
+        for (int g = W / 2, o = 0; g >= 1; o += g, g >>= 1) {
+            if (have) {
+#pragma unroll
+                for (int k = 0; k < g; ++k) acc += ring[o + k];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (rem & g) {
+#pragma unroll
+                for (int k = 0; k < g; ++k) ring[o + k] = row(j + k);
+                j += g;
+            }
+        }
+        if (have) acc += ring[W - 1];
+#pragma unroll
+        for (int g = W / 2, o = 0; g >= 1; o += g, g >>= 1) {
+            if (rem & g) {
+#pragma unroll
+                for (int k = 0; k < g; ++k) acc += ring[o + k];
+            }
+        }
+    }
+    float* op = target >= 0 ? out + (size_t)target * (size_t)F : partial + (size_t)(~target) * (size_t)F;
+    if (valid && lane < nvec) *(f32x4*)(op + lane * 4) = acc;
 }
 
 // any F (including F % 4 != 0): lanes stride over single floats, 64 columns per pass.
@@ -406,9 +504,9 @@ struct SegArgs {
     float *out, *partial;
 };
 
-// 1-KiB rows (F in (128, 256], the headline shape): 16 rows in flight per wave, 16 waves per workgroup, plain
-// work-item order.  Round-1 sweep of 40 variants (U in {2,4,8,16} x waves in {4,8,16} x XCD-contiguous remap x
-// non-temporal loads, profiles/r01_tune_k1_L256.txt): 421-457 us, this one fastest; the XCD remap is 3-4 % slower.
+// 1-KiB rows (F in (128, 256], the headline shape) without weight: k_seg_window, a window of 16 rows per wave, 8 waves
+// per workgroup, non-temporal row loads (sweep of window depth x waves x nt: tools/tune_k1_window.py, DESIGN.md
+// section 3).  An XCD-contiguous remap of the work items was 3-4 % slower (profiles/r01_tune_k1_L256.txt).
 
 template <int RL, int VPL, int U, bool W, bool RS, bool NT, int TAG, int WPB, bool XCD>
 static void launch_seg3(const SegArgs& a, hipStream_t s) {
@@ -421,21 +519,55 @@ static void launch_seg3(const SegArgs& a, hipStream_t s) {
         a.wi_target, a.n_items, a.max_items, a.out, a.partial);
 }
 
+// the partial rows of the combine pass (TAG 1) were just written and are small: they are read with plain loads
 template <int RL, int VPL, int U, bool W, bool RS, int TAG>
 static void launch_seg(const SegArgs& a, hipStream_t s) {
-    if (g_opt_nt_loads)
-        launch_seg3<RL, VPL, U, W, RS, true, TAG, 4, false>(a, s);
-    else
-        launch_seg3<RL, VPL, U, W, RS, false, TAG, 4, false>(a, s);
+    if constexpr (TAG != 1) {
+        if (g_opt_nt_loads) return launch_seg3<RL, VPL, U, W, RS, true, TAG, 4, false>(a, s);
+    }
+    launch_seg3<RL, VPL, U, W, RS, false, TAG, 4, false>(a, s);
 }
 
+template <int W, bool NT, int TAG, int WPB>
+static void launch_window(const SegArgs& a, hipStream_t s) {
+    const unsigned grid = (unsigned)ceil_div(a.max_items, WPB);
+    if (grid == 0) return;
+    k_seg_window<W, NT, TAG, WPB><<<grid, WPB * 64, 0, s>>>(a.src, a.F, a.F / 4, a.src_row, a.wi_begin, a.wi_end,
+                                                          a.wi_target, a.n_items, a.max_items, a.out,
+                                                          a.partial);
+}
+
+#ifdef HGNN_K1_SWEEP
+// tools/tune_k1_window.py builds a library of its own with every variant and picks one through hgnn_set_option
+static int g_opt_k1_window = 16, g_opt_k1_waves = 8;
+template <int W, int TAG>
+static void launch_window_waves(const SegArgs& a, hipStream_t s) {
+#define HGNN_WV(WPB)                                                        \
+    if (g_opt_nt_loads && TAG != 1) launch_window<W, true, TAG, WPB>(a, s); \
+    else launch_window<W, false, TAG, WPB>(a, s)
+    if (g_opt_k1_waves == 4) { HGNN_WV(4); }
+    else if (g_opt_k1_waves == 8) { HGNN_WV(8); }
+    else { HGNN_WV(16); }
+#undef HGNN_WV
+}
 template <int TAG>
 static void launch_seg_headline(const SegArgs& a, hipStream_t s) {
-    if (g_opt_nt_loads)
-        launch_seg3<64, 1, 16, false, false, true, TAG, 16, false>(a, s);
-    else
-        launch_seg3<64, 1, 16, false, false, false, TAG, 16, false>(a, s);
+    if (g_opt_k1_window == 0) {  // control: the burst-then-drain kernel this one replaced, with a real nt hint
+        if (g_opt_nt_loads && TAG != 1) launch_seg3<64, 1, 16, false, false, true, TAG, 16, false>(a, s);
+        else launch_seg3<64, 1, 16, false, false, false, TAG, 16, false>(a, s);
+    } else if (g_opt_k1_window == 8) launch_window_waves<8, TAG>(a, s);
+    else if (g_opt_k1_window == 32) launch_window_waves<32, TAG>(a, s);
+    else launch_window_waves<16, TAG>(a, s);
 }
+#else
+template <int TAG>
+static void launch_seg_headline(const SegArgs& a, hipStream_t s) {
+    if constexpr (TAG != 1) {
+        if (g_opt_nt_loads) return launch_window<16, true, TAG, 8>(a, s);
+    }
+    launch_window<16, false, TAG, 8>(a, s);
+}
+#endif
 
 template <bool W, bool RS, int TAG>
 static int dispatch_seg(const SegArgs& a, hipStream_t s) {
@@ -477,6 +609,10 @@ extern "C" int hgnn_set_option(const char* name, int value) {
     HGNN_REQUIRE(name != nullptr, "hgnn_set_option: name is NULL");
     if (!strcmp(name, "nt_loads")) g_opt_nt_loads = value;
     else if (!strcmp(name, "nt_stores")) g_opt_nt_stores = value;
+#ifdef HGNN_K1_SWEEP
+    else if (!strcmp(name, "k1_window")) g_opt_k1_window = value;
+    else if (!strcmp(name, "k1_waves")) g_opt_k1_waves = value;
+#endif
     else if (!strcmp(name, "mlp_ablate")) g_opt_mlp_ablate = value & 31;
     else if (!strcmp(name, "mlp_split_variant")) g_opt_mlp_split_variant = value;
     else if (!strcmp(name, "mlp_split3_rows128")) {
