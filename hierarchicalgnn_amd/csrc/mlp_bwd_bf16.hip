@@ -20,9 +20,9 @@
 //     that owns the column (deterministic), written once per workgroup at the end (persistent workgroups);
 //     the bias gradient (column sums of dz') comes out of hgnn_wgrad_bf16 (colsum) instead.
 #include "mlp_split_common.h"
+#include "options.h"
 
 namespace hgnn {
-extern int g_opt_mlp_ablate;
 namespace bw {
 using namespace fs;
 

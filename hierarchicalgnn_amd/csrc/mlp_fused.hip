@@ -31,6 +31,7 @@
 //     handled by zero padding (see hgnn_mlp_desc in include/hgnn_hip.h); `save_pre`
 //     dumps the pre-LayerNorm outputs for the opt-in differentiable variant.
 #include "mlp_common.h"
+#include "options.h"
 
 namespace hgnn {
 

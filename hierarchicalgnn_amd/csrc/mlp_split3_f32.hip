@@ -21,6 +21,7 @@
 //     rows by LDS-DMA, as in the bf16 kernel;
 //   * output / skip rows are fp32 (16 bytes per lane and tile).
 #include "mlp_split_common.h"
+#include "options.h"
 
 namespace hgnn {
 namespace f3 {
@@ -534,7 +535,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_mlp_f32_split3(con
 #else
 #define HGNN_STAMPW(k) do { } while (0)
 #endif
-extern int g_opt_split3_one_wg;
 #define HGNN_KH_NS r128
 #define HGNN_KH_NW 8
 #define HGNN_KH_NJ 8

@@ -19,9 +19,9 @@
 // GEMMs are transposed as in the other kernels (A = W fragment, B = activations, D[f][e]): lane
 // (e = lane&15, g = lane>>4) holds features 16T + 4g + r of edge 16j + e.
 #include "mlp_split_common.h"
+#include "options.h"
 
 namespace hgnn {
-extern int g_opt_mlp_ablate;
 int g_opt_mlp_split_variant = -1;  // hgnn_set_option("mlp_split_variant"): -1 auto, 0 counted waits, 2 burst
 namespace fs {
 

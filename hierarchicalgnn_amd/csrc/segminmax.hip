@@ -14,14 +14,12 @@
 // long list, nor on which lane saw which row.  A NaN is never a candidate (strict comparisons), so a
 // list of NaN only is empty: out = 0, arg = M.  No atomics: every out / arg element is written once,
 // split destinations through int32 partial positions and a second pass.
-#include "common.h"
+#include "rows_common.h"
 #include <climits>
-#include <type_traits>
 
 namespace hgnn {
 namespace sarg {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef long long i64x2 __attribute__((ext_vector_type(2)));
@@ -309,51 +307,37 @@ __global__ __launch_bounds__(256) void k_arg_scatter(const int64_t* __restrict__
 
 // ------------------------------------------------------------------ dispatch
 struct ArgArgs {
-    const hgnn_plan* plan;
     const void* src;
     int F;
-    const int32_t* perm;
+    int64_t M;  // rows of src: the arg of an empty list
     void* out;
     int64_t* arg;
     void* partial;
     int32_t* partial_arg;
+    ItemView work, split;
 };
 
-template <int DT, int OP, int RL, int VPL, int U, int WPB>
-static void launch_wide(const ArgArgs& a, hipStream_t s) {
-    const hgnn_plan* p = a.plan;
-    const unsigned grid = (unsigned)ceil_div(p->max_work, WPB);
-    if (grid == 0) return;
-    k_seg_arg<DT, OP, RL, VPL, U, WPB><<<grid, WPB * 64, 0, s>>>(
-        a.src, a.F, a.F / 4, a.perm, p->wi_begin, p->wi_end, p->wi_target, p->counts + HGNN_CNT_WORK, p->max_work,
-        p->n_rows, a.out, a.arg, a.partial, a.partial_arg);
-}
+// by row shape: rows in flight per wave (UH at a 1-KiB-wide fp32 row, K1's headline tile), waves per workgroup
+constexpr int arg_rows_in_flight(int RL, int VPL, int UH) { return RL < 64 ? 4 : VPL == 1 ? UH : VPL == 2 ? 4 : 2; }
+constexpr int arg_waves(int RL, int VPL) { return RL == 64 && VPL == 1 ? 16 : 4; }
 
 template <int DT, int OP>
 static void run(const ArgArgs& a, bool wide, hipStream_t s) {
-    const hgnn_plan* p = a.plan;
-    constexpr int UH = DT == HGNN_DT_I64 ? 8 : 16;  // rows in flight at a 1-KiB-wide fp32 row (K1's headline tile)
+    const ItemView& v = a.work;
     if (!wide) {
-        const unsigned grid = (unsigned)ceil_div(p->max_work, kWavesPerBlock);
-        if (grid)
-            k_seg_arg_narrow<DT, OP><<<grid, kBlock, 0, s>>>(a.src, a.F, a.perm, p->wi_begin, p->wi_end,
-                                                             p->wi_target, p->counts + HGNN_CNT_WORK, p->max_work,
-                                                             p->n_rows, a.out, a.arg, a.partial, a.partial_arg);
+        launch_items<kWavesPerBlock>(k_seg_arg_narrow<DT, OP>, v.max_items, s, a.src, a.F, v.perm, v.begin, v.end,
+                                     v.target, v.n_items, v.max_items, a.M, a.out, a.arg, a.partial, a.partial_arg);
     } else {
-        const int nvec = a.F / 4;
-        if (nvec <= 4) launch_wide<DT, OP, 4, 1, 4, 4>(a, s);
-        else if (nvec <= 8) launch_wide<DT, OP, 8, 1, 4, 4>(a, s);
-        else if (nvec <= 16) launch_wide<DT, OP, 16, 1, 4, 4>(a, s);
-        else if (nvec <= 32) launch_wide<DT, OP, 32, 1, 4, 4>(a, s);
-        else if (nvec <= 64) launch_wide<DT, OP, 64, 1, UH, 16>(a, s);
-        else if (nvec <= 128) launch_wide<DT, OP, 64, 2, 4, 4>(a, s);
-        else launch_wide<DT, OP, 64, 4, 2, 4>(a, s);
+        for_row_shape<256>(a.F / 4, [&](auto rl, auto vpl) {
+            constexpr int RL = decltype(rl)::value, VPL = decltype(vpl)::value, WPB = arg_waves(RL, VPL);
+            constexpr int U = arg_rows_in_flight(RL, VPL, DT == HGNN_DT_I64 ? 8 : 16);
+            launch_items<WPB>(k_seg_arg<DT, OP, RL, VPL, U, WPB>, v.max_items, s, a.src, a.F, a.F / 4, v.perm, v.begin,
+                              v.end, v.target, v.n_items, v.max_items, a.M, a.out, a.arg, a.partial, a.partial_arg);
+        });
     }
-    const unsigned grid = (unsigned)ceil_div(p->max_split, kWavesPerBlock);
-    if (grid)
-        k_arg_combine<DT, OP><<<grid, kBlock, 0, s>>>(a.partial, a.partial_arg, a.F, p->split_dst, p->split_pbegin,
-                                                      p->counts + HGNN_CNT_SPLIT, p->max_split, p->n_rows, a.out,
-                                                      a.arg);
+    const ItemView& c = a.split;
+    launch_items<kWavesPerBlock>(k_arg_combine<DT, OP>, c.max_items, s, a.partial, a.partial_arg, a.F, c.target,
+                                 c.begin, c.n_items, c.max_items, a.M, a.out, a.arg);
 }
 
 template <int DT>
@@ -404,16 +388,9 @@ extern "C" int hgnn_segment_reduce_ex(const hgnn_plan* plan, int32_t op, int32_t
     const uintptr_t al = (uintptr_t)(4 * eb < 16 ? 4 * eb : 16);
     const bool wide = F % 4 == 0 && F <= 1024 && (uintptr_t)src % al == 0 && (uintptr_t)out % al == 0 &&
                       (uintptr_t)partial % al == 0 && (uintptr_t)arg % 16 == 0 && (uintptr_t)partial_arg % 16 == 0;
-    ArgArgs a;
-    a.plan = plan;
-    a.src = src;
-    a.F = F;
+    ArgArgs a = {src, F, plan->n_rows, out, arg, partial, partial_arg, work_items(plan), split_items(plan)};
     // position of sorted entry p = its row in src: perm[p], or p itself on an already sorted index
-    a.perm = plan->src_row != nullptr ? plan->perm : nullptr;
-    a.out = out;
-    a.arg = arg;
-    a.partial = partial;
-    a.partial_arg = partial_arg;
+    if (plan->src_row == nullptr) a.work.perm = nullptr;
     if (op == HGNN_RED_SUM) {
         if (dtype == HGNN_DT_I32) run<HGNN_DT_I32, HGNN_RED_SUM>(a, wide, stream);
         else run<HGNN_DT_I64, HGNN_RED_SUM>(a, wide, stream);
@@ -442,14 +419,13 @@ extern "C" int hgnn_segment_arg_backward(const int64_t* arg, int64_t n_dst, int3
     HGNN_CHECK_HIP(hipMemsetAsync(grad_src, 0, (size_t)n_rows * (size_t)F * (size_t)eb, stream));
     const int64_t total = n_dst * (int64_t)F;
     if (total > 0) {
-        int64_t blocks = ceil_div(total, kBlock);
-        if (blocks > 256 * 8 * 4) blocks = 256 * 8 * 4;
+        const unsigned blocks = capped_grid(ceil_div(total, kBlock));
         if (dtype == HGNN_DT_F32)
-            k_arg_scatter<float><<<(unsigned)blocks, kBlock, 0, stream>>>(arg, (const float*)grad_out, total, F,
-                                                                          n_rows, (float*)grad_src);
+            k_arg_scatter<float><<<blocks, kBlock, 0, stream>>>(arg, (const float*)grad_out, total, F, n_rows,
+                                                                (float*)grad_src);
         else
-            k_arg_scatter<uint16_t><<<(unsigned)blocks, kBlock, 0, stream>>>(arg, (const uint16_t*)grad_out, total, F,
-                                                                             n_rows, (uint16_t*)grad_src);
+            k_arg_scatter<uint16_t><<<blocks, kBlock, 0, stream>>>(arg, (const uint16_t*)grad_out, total, F, n_rows,
+                                                                   (uint16_t*)grad_src);
     }
     HGNN_CHECK_HIP(hipGetLastError());
     return HGNN_OK;

@@ -17,20 +17,12 @@
 // One wave owns one work item (= one destination, or one chunk of a long
 // list): no atomics, every output row is written exactly once with 16-B
 // stores, and the summation order is fixed by the plan.
-#include "common.h"
-#include <cstdlib>
-#include <cstring>
+#include "rows_common.h"
 
 namespace hgnn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-extern int g_opt_mlp_ablate;
-extern int g_opt_mlp_split_variant;
-namespace f3 { extern int g_opt_split3_rows128; extern int g_opt_split3_one_wg; }
-
-static int g_opt_nt_loads = 1;   // non-temporal loads for once-read source rows
-static int g_opt_nt_stores = 0;  // non-temporal stores for gather output
+int g_opt_nt_loads = 1;   // hgnn_set_option("nt_loads"): non-temporal loads for once-read source rows
+int g_opt_nt_stores = 0;  // hgnn_set_option("nt_stores"): non-temporal stores for gather output
 
 // NT is a template parameter on purpose: written as `nt ? nontemporal_load(p) : *p` with a function argument,
 // both arms load the same address, the helper is optimised before it is inlined, and the two loads are merged
@@ -157,8 +149,8 @@ __global__ __launch_bounds__(WPB * 64) void k_seg_reduce(
 // sorted-layout and combine instantiations drain with vmcnt(W-1), W-2, ..  
 // Rows are added one by one in list order, starting from 0: the sum is bitwise the one of k_seg_reduce.
 // TAG 0 reads its rows through src_row; TAG 1 (combine) and TAG 2 (sorted layout) read rows begin..end-1.
-// Reads before the count is known: wi_begin, wi_end and wi_target need max_items entries each; in the combine
-// pass wi_end is split_pbegin + 1, so split_pbegin needs max_split + 1 entries (include/hgnn_hip.h, hgnn_plan).
+// Reads before the count is known: wi_begin, wi_end and wi_target need max_items entries each (the combine pass:
+// split_items, rows_common.h).
 template <int W, bool NT, int TAG, int WPB>
 __global__ __launch_bounds__(WPB * 64) void k_seg_window(
     const float* __restrict__ src, int F, int nvec, const int32_t* __restrict__ src_row,
@@ -495,142 +487,92 @@ __global__ __launch_bounds__(256) void k_edge_dot_scalar(const float* __restrict
 struct SegArgs {
     const float* src;
     int F;
-    const int32_t* src_row;
-    const int32_t* perm;
     const float* weight;
     const float* row_scale;
-    const int32_t *wi_begin, *wi_end, *wi_target, *n_items;
-    int64_t max_items;
     float *out, *partial;
+    ItemView items;
 };
 
-// 1-KiB rows (F in (128, 256], the headline shape) without weight: k_seg_window, a window of 16 rows per wave, 8 waves
-// per workgroup, non-temporal row loads (sweep of window depth x waves x nt: tools/tune_k1_window.py, DESIGN.md
-// section 3).  An XCD-contiguous remap of the work items was 3-4 % slower (profiles/r01_tune_k1_L256.txt).
-
-template <int RL, int VPL, int U, bool W, bool RS, bool NT, int TAG, int WPB, bool XCD>
-static void launch_seg3(const SegArgs& a, hipStream_t s) {
-    unsigned grid = (unsigned)ceil_div(a.max_items, WPB);
-    if (grid == 0) return;
-    if (XCD) grid = (grid + 7) / 8 * 8;
-    const int nvec = a.F / 4;
-    k_seg_reduce<RL, VPL, U, W, RS, NT, TAG, WPB, XCD><<<grid, WPB * 64, 0, s>>>(
-        a.src, a.F, nvec, a.src_row, a.perm, a.weight, a.row_scale, a.wi_begin, a.wi_end,
-        a.wi_target, a.n_items, a.max_items, a.out, a.partial);
+// The one place that decides on non-temporal row loads: fn(bool_constant<NT>).  The partial rows of the combine
+// pass (TAG 1) were just written and are small: they are read with plain loads, and no NT kernel exists for them.
+template <int TAG, class Fn>
+static void with_nt_loads(Fn&& fn) {
+    if constexpr (TAG != 1) {
+        if (g_opt_nt_loads) return fn(std::true_type{});
+    }
+    fn(std::false_type{});
 }
 
-// the partial rows of the combine pass (TAG 1) were just written and are small: they are read with plain loads
+template <int RL, int VPL, int U, bool W, bool RS, bool NT, int TAG, int WPB>
+static void launch_seg3(const SegArgs& a, hipStream_t s) {
+    const ItemView& v = a.items;
+    launch_items<WPB>(k_seg_reduce<RL, VPL, U, W, RS, NT, TAG, WPB, false>, v.max_items, s, a.src, a.F, a.F / 4,
+                      v.src_row, v.perm, a.weight, a.row_scale, v.begin, v.end, v.target, v.n_items, v.max_items,
+                      a.out, a.partial);
+}
+
 template <int RL, int VPL, int U, bool W, bool RS, int TAG>
 static void launch_seg(const SegArgs& a, hipStream_t s) {
-    if constexpr (TAG != 1) {
-        if (g_opt_nt_loads) return launch_seg3<RL, VPL, U, W, RS, true, TAG, 4, false>(a, s);
-    }
-    launch_seg3<RL, VPL, U, W, RS, false, TAG, 4, false>(a, s);
+    with_nt_loads<TAG>([&](auto nt) { launch_seg3<RL, VPL, U, W, RS, decltype(nt)::value, TAG, 4>(a, s); });
 }
 
 template <int W, bool NT, int TAG, int WPB>
 static void launch_window(const SegArgs& a, hipStream_t s) {
-    const unsigned grid = (unsigned)ceil_div(a.max_items, WPB);
-    if (grid == 0) return;
-    k_seg_window<W, NT, TAG, WPB><<<grid, WPB * 64, 0, s>>>(a.src, a.F, a.F / 4, a.src_row, a.wi_begin, a.wi_end,
-                                                          a.wi_target, a.n_items, a.max_items, a.out,
-                                                          a.partial);
+    const ItemView& v = a.items;
+    launch_items<WPB>(k_seg_window<W, NT, TAG, WPB>, v.max_items, s, a.src, a.F, a.F / 4, v.src_row, v.begin, v.end,
+                      v.target, v.n_items, v.max_items, a.out, a.partial);
 }
 
 #ifdef HGNN_K1_SWEEP
 // tools/tune_k1_window.py builds a library of its own with every variant and picks one through hgnn_set_option
-static int g_opt_k1_window = 16, g_opt_k1_waves = 8;
-template <int W, int TAG>
-static void launch_window_waves(const SegArgs& a, hipStream_t s) {
-#define HGNN_WV(WPB)                                                        \
-    if (g_opt_nt_loads && TAG != 1) launch_window<W, true, TAG, WPB>(a, s); \
-    else launch_window<W, false, TAG, WPB>(a, s)
-    if (g_opt_k1_waves == 4) { HGNN_WV(4); }
-    else if (g_opt_k1_waves == 8) { HGNN_WV(8); }
-    else { HGNN_WV(16); }
-#undef HGNN_WV
-}
-template <int TAG>
-static void launch_seg_headline(const SegArgs& a, hipStream_t s) {
-    if (g_opt_k1_window == 0) {  // control: the burst-then-drain kernel this one replaced, with a real nt hint
-        if (g_opt_nt_loads && TAG != 1) launch_seg3<64, 1, 16, false, false, true, TAG, 16, false>(a, s);
-        else launch_seg3<64, 1, 16, false, false, false, TAG, 16, false>(a, s);
-    } else if (g_opt_k1_window == 8) launch_window_waves<8, TAG>(a, s);
-    else if (g_opt_k1_window == 32) launch_window_waves<32, TAG>(a, s);
-    else launch_window_waves<16, TAG>(a, s);
-}
-#else
-template <int TAG>
-static void launch_seg_headline(const SegArgs& a, hipStream_t s) {
-    if constexpr (TAG != 1) {
-        if (g_opt_nt_loads) return launch_window<16, true, TAG, 8>(a, s);
-    }
-    launch_window<16, false, TAG, 8>(a, s);
-}
+int g_opt_k1_window = 16, g_opt_k1_waves = 8;
 #endif
 
-template <bool W, bool RS, int TAG>
-static int dispatch_seg(const SegArgs& a, hipStream_t s) {
-    const int F = a.F;
-    if (F % 4 != 0 || F > 1024) {
-        const unsigned grid = (unsigned)ceil_div(a.max_items, kWavesPerBlock);
-        if (grid)
-            k_seg_reduce_scalar<W, RS><<<grid, kBlock, 0, s>>>(a.src, F, a.src_row, a.perm, a.weight,
-                                                               a.row_scale, a.wi_begin, a.wi_end,
-                                                               a.wi_target, a.n_items, a.max_items,
-                                                               a.out, a.partial);
-        return HGNN_OK;
-    }
-    const int nvec = F / 4;
-    if (nvec <= 4) launch_seg<4, 1, 4, W, RS, TAG>(a, s);
-    else if (nvec <= 8) launch_seg<8, 1, 4, W, RS, TAG>(a, s);
-    else if (nvec <= 16) launch_seg<16, 1, 4, W, RS, TAG>(a, s);
-    else if (nvec <= 32) launch_seg<32, 1, 4, W, RS, TAG>(a, s);  // (U8 / 16-wave variants: within 1 %)
-    else if (nvec <= 64) {
-        if (!W && !RS) launch_seg_headline<TAG>(a, s);
-        else launch_seg<64, 1, 8, W, RS, TAG>(a, s);
-    } else if (nvec <= 128) launch_seg<64, 2, 4, W, RS, TAG>(a, s);
-    else launch_seg<64, 4, 2, W, RS, TAG>(a, s);
-    return HGNN_OK;
+// 1-KiB rows (F in (128, 256], the headline shape) without weight: k_seg_window, a window of 16 rows per wave, 8 waves
+// per workgroup, non-temporal row loads (sweep of window depth x waves x nt: tools/tune_k1_window.py, DESIGN.md
+// section 3).  An XCD-contiguous remap of the work items was 3-4 % slower (profiles/r01_tune_k1_L256.txt).
+template <int TAG>
+static void launch_seg_headline(const SegArgs& a, hipStream_t s) {
+    with_nt_loads<TAG>([&](auto nt) {
+        constexpr bool NT = decltype(nt)::value;
+#ifdef HGNN_K1_SWEEP
+        auto waves = [&](auto w) {
+            constexpr int W = decltype(w)::value;
+            if (g_opt_k1_waves == 4) launch_window<W, NT, TAG, 4>(a, s);
+            else if (g_opt_k1_waves == 8) launch_window<W, NT, TAG, 8>(a, s);
+            else launch_window<W, NT, TAG, 16>(a, s);
+        };
+        // window 0 = control: the burst-then-drain kernel this one replaced, with a real nt hint
+        if (g_opt_k1_window == 0) launch_seg3<64, 1, 16, false, false, NT, TAG, 16>(a, s);
+        else if (g_opt_k1_window == 8) waves(std::integral_constant<int, 8>{});
+        else if (g_opt_k1_window == 32) waves(std::integral_constant<int, 32>{});
+        else waves(std::integral_constant<int, 16>{});
+#else
+        launch_window<16, NT, TAG, 8>(a, s);
+#endif
+    });
 }
 
-static unsigned stream_grid(int64_t n_tiles) {
-    int64_t blocks = ceil_div(n_tiles, kWavesPerBlock);
-    const int64_t cap = 256 * 8 * 4;  // 256 CUs x 8 blocks, x4 for balance
-    if (blocks > cap) blocks = cap;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
+// rows in flight per wave, by row shape  (RL 32: U8 / 16-wave variants were within 1 %)
+constexpr int seg_rows_in_flight(int RL, int VPL) { return RL < 64 ? 4 : VPL == 1 ? 8 : VPL == 2 ? 4 : 2; }
+
+template <bool W, bool RS, int TAG>
+static void dispatch_seg(const SegArgs& a, hipStream_t s) {
+    const ItemView& v = a.items;
+    if (a.F % 4 != 0 || a.F > 1024)
+        return launch_items<kWavesPerBlock>(k_seg_reduce_scalar<W, RS>, v.max_items, s, a.src, a.F, v.src_row, v.perm,
+                                            a.weight, a.row_scale, v.begin, v.end, v.target, v.n_items, v.max_items,
+                                            a.out, a.partial);
+    for_row_shape<256>(a.F / 4, [&](auto rl, auto vpl) {
+        constexpr int RL = decltype(rl)::value, VPL = decltype(vpl)::value;
+        if constexpr (RL == 64 && VPL == 1 && !W && !RS) launch_seg_headline<TAG>(a, s);
+        else launch_seg<RL, VPL, seg_rows_in_flight(RL, VPL), W, RS, TAG>(a, s);
+    });
 }
 
 }  // namespace hgnn
 
 using namespace hgnn;
-
-extern "C" int hgnn_set_option(const char* name, int value) {
-    HGNN_REQUIRE(name != nullptr, "hgnn_set_option: name is NULL");
-    if (!strcmp(name, "nt_loads")) g_opt_nt_loads = value;
-    else if (!strcmp(name, "nt_stores")) g_opt_nt_stores = value;
-#ifdef HGNN_K1_SWEEP
-    else if (!strcmp(name, "k1_window")) g_opt_k1_window = value;
-    else if (!strcmp(name, "k1_waves")) g_opt_k1_waves = value;
-#endif
-    else if (!strcmp(name, "mlp_ablate")) g_opt_mlp_ablate = value & 31;
-    else if (!strcmp(name, "mlp_split_variant")) g_opt_mlp_split_variant = value;
-    else if (!strcmp(name, "mlp_split3_rows128")) {
-        // 2 = the two-workgroup tile that returned wrong elements in one of two equivalent builds:
-        // measurement tools only, behind an environment switch of its own
-        if (value < 0 || value > 2 || (value == 2 && getenv("HGNN_EXPERIMENTAL") == nullptr)) {
-            set_error("hgnn_set_option: mlp_split3_rows128 takes 0 or 1 (2 = experimental tile, needs HGNN_EXPERIMENTAL=1)");
-            return HGNN_ERR_INVALID_ARG;
-        }
-        f3::g_opt_split3_rows128 = value;
-    }
-    else if (!strcmp(name, "mlp_split3_one_wg")) f3::g_opt_split3_one_wg = value;
-    else {
-        set_error("hgnn_set_option: unknown option '%s'", name);
-        return HGNN_ERR_INVALID_ARG;
-    }
-    return HGNN_OK;
-}
 
 extern "C" int hgnn_segment_reduce_f32(const hgnn_plan* plan, const float* src, int32_t F,
                                        const float* weight, const float* row_scale, float* out,
@@ -646,73 +588,37 @@ extern "C" int hgnn_segment_reduce_f32(const hgnn_plan* plan, const float* src, 
     HGNN_REQUIRE(partial != nullptr || plan->max_partial == 0, "hgnn_segment_reduce_f32: partial is NULL");
     HGNN_REQUIRE(((uintptr_t)src % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)partial % 16 == 0) || F % 4 != 0,
                  "hgnn_segment_reduce_f32: src/out/partial must be 16-byte aligned");
-    SegArgs a;
-    a.src = src;
-    a.F = F;
-    a.src_row = plan->src_row;
-    a.perm = plan->perm;
-    a.weight = weight;
-    a.row_scale = row_scale;
-    a.wi_begin = plan->wi_begin;
-    a.wi_end = plan->wi_end;
-    a.wi_target = plan->wi_target;
-    a.n_items = plan->counts + HGNN_CNT_WORK;
-    a.max_items = plan->max_work;
-    a.out = out;
-    a.partial = partial;
-    int rc;
-    if (weight && row_scale) rc = dispatch_seg<true, true, 0>(a, stream);
-    else if (weight) rc = dispatch_seg<true, false, 0>(a, stream);
+    const SegArgs a = {src, F, weight, row_scale, out, partial, work_items(plan)};
+    if (weight && row_scale) dispatch_seg<true, true, 0>(a, stream);
+    else if (weight) dispatch_seg<true, false, 0>(a, stream);
     else if (row_scale) {
         set_error("hgnn_segment_reduce_f32: row_scale requires weight");
         return HGNN_ERR_UNSUPPORTED;
     } else if (plan->src_row == nullptr) {
-        rc = dispatch_seg<false, false, 2>(a, stream);  // TAG 2: sorted-layout (streaming) launches, named apart in profiles
-    } else rc = dispatch_seg<false, false, 0>(a, stream);
-    if (rc != HGNN_OK) return rc;
+        dispatch_seg<false, false, 2>(a, stream);  // TAG 2: sorted-layout (streaming) launches, named apart in profiles
+    } else dispatch_seg<false, false, 0>(a, stream);
     // second pass: sum the partial rows of split destinations, in chunk order
-    SegArgs b;
-    b.src = partial;
-    b.F = F;
-    b.src_row = nullptr;
-    b.perm = nullptr;
-    b.weight = nullptr;
-    b.row_scale = nullptr;
-    b.wi_begin = plan->split_pbegin;
-    b.wi_end = plan->split_pbegin + 1;
-    b.wi_target = plan->split_dst;
-    b.n_items = plan->counts + HGNN_CNT_SPLIT;
-    b.max_items = plan->max_split;
-    b.out = out;
-    b.partial = partial;
-    rc = dispatch_seg<false, false, 1>(b, stream);
-    if (rc != HGNN_OK) return rc;
+    dispatch_seg<false, false, 1>(SegArgs{partial, F, nullptr, nullptr, out, partial, split_items(plan)}, stream);
     HGNN_CHECK_HIP(hipGetLastError());
     return HGNN_OK;
 }
 
+constexpr int gather_rows_in_flight(int RL, int VPL) { return RL <= 8 ? 2 : RL < 64 ? 4 : VPL == 1 ? 8 : VPL == 2 ? 4 : 2; }
+
 template <bool W, bool RS>
-static int dispatch_gather(const float* table, int F, const int32_t* idx, int64_t M, const float* weight,
-                           const float* row_scale, float* out, hipStream_t s) {
-    const int64_t n_tiles = ceil_div(M, 64);
+static void dispatch_gather(const float* table, int F, const int32_t* idx, int64_t M, const float* weight,
+                            const float* row_scale, float* out, hipStream_t s) {
     if (F % 4 != 0 || F > 1024) {
         k_gather_rows_scalar<W, RS><<<stream_grid(M), kBlock, 0, s>>>(table, F, idx, M, weight, row_scale, out);
-        return HGNN_OK;
+        return;
     }
-    const int nvec = F / 4;
-    const unsigned grid = stream_grid(n_tiles);
+    const unsigned grid = stream_grid(ceil_div(M, 64));
     const bool nt = g_opt_nt_stores != 0;
-#define HGNN_G(RL, VPL, U) \
-    k_gather_rows<RL, VPL, U, W, RS><<<grid, kBlock, 0, s>>>(table, F, nvec, idx, M, weight, row_scale, out, nt)
-    if (nvec <= 4) HGNN_G(4, 1, 2);
-    else if (nvec <= 8) HGNN_G(8, 1, 2);
-    else if (nvec <= 16) HGNN_G(16, 1, 4);
-    else if (nvec <= 32) HGNN_G(32, 1, 4);
-    else if (nvec <= 64) HGNN_G(64, 1, 8);
-    else if (nvec <= 128) HGNN_G(64, 2, 4);
-    else HGNN_G(64, 4, 2);
-#undef HGNN_G
-    return HGNN_OK;
+    for_row_shape<256>(F / 4, [&](auto rl, auto vpl) {
+        constexpr int RL = decltype(rl)::value, VPL = decltype(vpl)::value;
+        k_gather_rows<RL, VPL, gather_rows_in_flight(RL, VPL), W, RS><<<grid, kBlock, 0, s>>>(
+            table, F, F / 4, idx, M, weight, row_scale, out, nt);
+    });
 }
 
 extern "C" int hgnn_gather_rows_f32(const float* table, int64_t table_rows, int32_t F, const int32_t* idx,
@@ -724,47 +630,28 @@ extern "C" int hgnn_gather_rows_f32(const float* table, int64_t table_rows, int3
     HGNN_REQUIRE(table != nullptr && idx != nullptr && out != nullptr, "hgnn_gather_rows_f32: NULL pointer");
     HGNN_REQUIRE(((uintptr_t)table % 16 == 0 && (uintptr_t)out % 16 == 0) || F % 4 != 0,
                  "hgnn_gather_rows_f32: table/out must be 16-byte aligned");
-    int rc;
-    if (weight && row_scale) rc = dispatch_gather<true, true>(table, F, idx, M, weight, row_scale, out, stream);
-    else if (weight) rc = dispatch_gather<true, false>(table, F, idx, M, weight, row_scale, out, stream);
-    else if (row_scale) rc = dispatch_gather<false, true>(table, F, idx, M, weight, row_scale, out, stream);
-    else rc = dispatch_gather<false, false>(table, F, idx, M, weight, row_scale, out, stream);
-    if (rc != HGNN_OK) return rc;
+    if (weight && row_scale) dispatch_gather<true, true>(table, F, idx, M, weight, row_scale, out, stream);
+    else if (weight) dispatch_gather<true, false>(table, F, idx, M, weight, row_scale, out, stream);
+    else if (row_scale) dispatch_gather<false, true>(table, F, idx, M, weight, row_scale, out, stream);
+    else dispatch_gather<false, false>(table, F, idx, M, weight, row_scale, out, stream);
     HGNN_CHECK_HIP(hipGetLastError());
     return HGNN_OK;
 }
 
+constexpr int spread_waves(int RL) { return RL < 64 ? 4 : 8; }  // per workgroup
+
 template <bool W>
-static int dispatch_spread(const hgnn_plan* plan, const float* table, int F, const float* weight, float* out,
-                           hipStream_t s) {
-    const int64_t max_items = plan->max_work;
-    const int32_t* n_items = plan->counts + HGNN_CNT_WORK;
-    if (F % 4 != 0 || F > 1024) {
-        const unsigned grid = (unsigned)ceil_div(max_items, kWavesPerBlock);
-        if (grid)
-            k_spread_rows_scalar<W><<<grid, kBlock, 0, s>>>(table, F, plan->perm, weight, plan->wi_begin,
-                                                           plan->wi_end, plan->wi_dst, n_items, max_items, out);
-        return HGNN_OK;
-    }
-    const int nvec = F / 4;
+static void dispatch_spread(const ItemView& v, const float* table, int F, const float* weight, float* out,
+                            hipStream_t s) {
+    if (F % 4 != 0 || F > 1024)
+        return launch_items<kWavesPerBlock>(k_spread_rows_scalar<W>, v.max_items, s, table, F, v.perm, weight, v.begin,
+                                            v.end, v.wi_dst, v.n_items, v.max_items, out);
     const bool nt = g_opt_nt_stores != 0;
-#define HGNN_S(RL, VPL, WPB)                                                                          \
-    do {                                                                                              \
-        const unsigned grid = (unsigned)ceil_div(max_items, WPB);                                     \
-        if (grid)                                                                                     \
-            k_spread_rows<RL, VPL, W, WPB><<<grid, WPB * 64, 0, s>>>(table, F, nvec, plan->perm, weight,   \
-                                                                     plan->wi_begin, plan->wi_end,    \
-                                                                     plan->wi_dst, n_items, max_items, out, nt); \
-    } while (0)
-    if (nvec <= 4) HGNN_S(4, 1, 4);
-    else if (nvec <= 8) HGNN_S(8, 1, 4);
-    else if (nvec <= 16) HGNN_S(16, 1, 4);
-    else if (nvec <= 32) HGNN_S(32, 1, 4);
-    else if (nvec <= 64) HGNN_S(64, 1, 8);
-    else if (nvec <= 128) HGNN_S(64, 2, 8);
-    else HGNN_S(64, 4, 8);
-#undef HGNN_S
-    return HGNN_OK;
+    for_row_shape<256>(F / 4, [&](auto rl, auto vpl) {
+        constexpr int RL = decltype(rl)::value, VPL = decltype(vpl)::value, WPB = spread_waves(RL);
+        launch_items<WPB>(k_spread_rows<RL, VPL, W, WPB>, v.max_items, s, table, F, F / 4, v.perm, weight, v.begin,
+                          v.end, v.wi_dst, v.n_items, v.max_items, out, nt);
+    });
 }
 
 extern "C" int hgnn_spread_rows_f32(const hgnn_plan* plan, const float* table, int32_t F, const float* weight,
@@ -777,9 +664,8 @@ extern "C" int hgnn_spread_rows_f32(const hgnn_plan* plan, const float* table, i
     HGNN_REQUIRE(table != nullptr && out != nullptr, "hgnn_spread_rows_f32: NULL pointer");
     HGNN_REQUIRE(((uintptr_t)table % 16 == 0 && (uintptr_t)out % 16 == 0) || F % 4 != 0,
                  "hgnn_spread_rows_f32: table/out must be 16-byte aligned");
-    int rc = weight ? dispatch_spread<true>(plan, table, F, weight, out, stream)
-                    : dispatch_spread<false>(plan, table, F, weight, out, stream);
-    if (rc != HGNN_OK) return rc;
+    if (weight) dispatch_spread<true>(work_items(plan), table, F, weight, out, stream);
+    else dispatch_spread<false>(work_items(plan), table, F, weight, out, stream);
     HGNN_CHECK_HIP(hipGetLastError());
     return HGNN_OK;
 }
@@ -793,21 +679,14 @@ extern "C" int hgnn_edge_dot_f32(const float* A, const int32_t* ai, int64_t a_ro
     HGNN_REQUIRE(A != nullptr && B != nullptr && out != nullptr, "hgnn_edge_dot_f32: NULL pointer");
     HGNN_REQUIRE((ai != nullptr || a_rows >= M) && (bi != nullptr || b_rows >= M),
                  "hgnn_edge_dot_f32: identity-indexed operand has fewer than M rows");
-    const int64_t n_tiles = ceil_div(M, 64);
     if (F % 4 != 0 || F > 1024 || (uintptr_t)A % 16 != 0 || (uintptr_t)B % 16 != 0) {
         k_edge_dot_scalar<<<stream_grid(M), kBlock, 0, stream>>>(A, ai, B, bi, F, M, out);
     } else {
-        const int nvec = F / 4;
-        const unsigned grid = stream_grid(n_tiles);
-#define HGNN_D(RL, VPL) k_edge_dot<RL, VPL><<<grid, kBlock, 0, stream>>>(A, ai, B, bi, F, nvec, M, out)
-        if (nvec <= 4) HGNN_D(4, 1);
-        else if (nvec <= 8) HGNN_D(8, 1);
-        else if (nvec <= 16) HGNN_D(16, 1);
-        else if (nvec <= 32) HGNN_D(32, 1);
-        else if (nvec <= 64) HGNN_D(64, 1);
-        else if (nvec <= 128) HGNN_D(64, 2);
-        else HGNN_D(64, 4);
-#undef HGNN_D
+        const unsigned grid = stream_grid(ceil_div(M, 64));
+        for_row_shape<256>(F / 4, [&](auto rl, auto vpl) {
+            k_edge_dot<decltype(rl)::value, decltype(vpl)::value><<<grid, kBlock, 0, stream>>>(A, ai, B, bi, F, F / 4, M,
+                                                                                              out);
+        });
     }
     HGNN_CHECK_HIP(hipGetLastError());
     return HGNN_OK;

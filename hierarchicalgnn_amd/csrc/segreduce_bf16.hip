@@ -4,12 +4,10 @@
 // (v_cvt_pk_bf16_f32), so the result does not depend on the list length the way bf16 atomics would
 // (MI355X_MICROARCH.md, global float atomics: pk_add_bf16 rounds every add).
 // Partial sums of split lists stay fp32; the combine pass rounds once.
-#include "common.h"
-#include <type_traits>
+#include "rows_common.h"
 
 namespace hgnn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -241,28 +239,16 @@ __global__ __launch_bounds__(256) void k_gather_rows_bf16(const unsigned short* 
 
 static bool bf16_shape_ok(int F) { return F > 0 && F % 8 == 0 && F <= 512; }
 
-template <int RL, int U, int WPB>
-static void launch_seg_bf16(const hgnn_plan* plan, const void* src, int F, const float* weight,
-                            const float* row_scale, unsigned short* out, float* partial, hipStream_t s) {
-    const int ncol = F / 8;
-    const unsigned grid = (unsigned)ceil_div(plan->max_work, WPB);
-    const int32_t* n_items = plan->counts + HGNN_CNT_WORK;
-#define HGNN_B(W_, RS_)                                                                                   \
-    k_seg_reduce_bf16<RL, U, W_, RS_, false, WPB><<<grid, WPB * 64, 0, s>>>(                              \
-        src, F, ncol, plan->src_row, plan->perm, weight, row_scale, plan->wi_begin, plan->wi_end,         \
-        plan->wi_target, n_items, plan->max_work, out, partial)
-    if (grid) {
-        if (weight && row_scale) HGNN_B(true, true);
-        else if (weight) HGNN_B(true, false);
-        else HGNN_B(false, false);
-    }
-#undef HGNN_B
-    // combine pass: fp32 partial rows -> bf16 output rows of the split destinations
-    const unsigned grid2 = (unsigned)ceil_div(plan->max_split, 4);
-    if (grid2)
-        k_seg_reduce_bf16<RL, 4, false, false, true, 4><<<grid2, 256, 0, s>>>(
-            partial, F, ncol, nullptr, nullptr, nullptr, nullptr, plan->split_pbegin, plan->split_pbegin + 1,
-            plan->split_dst, plan->counts + HGNN_CNT_SPLIT, plan->max_split, out, partial);
+// main pass by row shape: rows in flight per wave, waves per workgroup
+constexpr int seg_bf16_rows_in_flight(int RL) { return RL < 64 ? 4 : 16; }
+constexpr int seg_bf16_waves(int RL) { return RL < 32 ? 4 : RL == 32 ? 8 : 16; }
+
+// IN_F32 false: the main pass over bf16 rows; true: the combine pass, fp32 partial rows -> bf16 output rows
+template <int RL, int U, bool W, bool RS, bool IN_F32, int WPB>
+static void launch_seg_bf16(const ItemView& v, const void* src, int F, const float* weight, const float* row_scale,
+                            unsigned short* out, float* partial, hipStream_t s) {
+    launch_items<WPB>(k_seg_reduce_bf16<RL, U, W, RS, IN_F32, WPB>, v.max_items, s, src, F, F / 8, v.src_row, v.perm,
+                      weight, row_scale, v.begin, v.end, v.target, v.n_items, v.max_items, out, partial);
 }
 
 }  // namespace hgnn
@@ -286,13 +272,19 @@ extern "C" int hgnn_segment_reduce_bf16(const hgnn_plan* plan, const void* src, 
                  "hgnn_segment_reduce_bf16: src_row may only be NULL for a sorted plan without gather");
     HGNN_REQUIRE((uintptr_t)src % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)partial % 16 == 0,
                  "hgnn_segment_reduce_bf16: src/out/partial must be 16-byte aligned");
-    const int ncol = F / 8;
     unsigned short* o = (unsigned short*)out;
-    if (ncol <= 4) launch_seg_bf16<4, 4, 4>(plan, src, F, weight, row_scale, o, partial, stream);
-    else if (ncol <= 8) launch_seg_bf16<8, 4, 4>(plan, src, F, weight, row_scale, o, partial, stream);
-    else if (ncol <= 16) launch_seg_bf16<16, 4, 4>(plan, src, F, weight, row_scale, o, partial, stream);
-    else if (ncol <= 32) launch_seg_bf16<32, 4, 8>(plan, src, F, weight, row_scale, o, partial, stream);
-    else launch_seg_bf16<64, 16, 16>(plan, src, F, weight, row_scale, o, partial, stream);
+    for_row_shape<64>(F / 8, [&](auto rl, auto) {
+        constexpr int RL = decltype(rl)::value, U = seg_bf16_rows_in_flight(RL), WPB = seg_bf16_waves(RL);
+        const ItemView v = work_items(plan);
+        if (weight && row_scale)
+            launch_seg_bf16<RL, U, true, true, false, WPB>(v, src, F, weight, row_scale, o, partial, stream);
+        else if (weight)
+            launch_seg_bf16<RL, U, true, false, false, WPB>(v, src, F, weight, row_scale, o, partial, stream);
+        else
+            launch_seg_bf16<RL, U, false, false, false, WPB>(v, src, F, weight, row_scale, o, partial, stream);
+        launch_seg_bf16<RL, 4, false, false, true, 4>(split_items(plan), partial, F, nullptr, nullptr, o, partial,
+                                                      stream);
+    });
     HGNN_CHECK_HIP(hipGetLastError());
     return HGNN_OK;
 }
@@ -310,26 +302,18 @@ extern "C" int hgnn_spread_rows_bf16(const hgnn_plan* plan, const void* table, i
     HGNN_REQUIRE(table != nullptr && out != nullptr, "hgnn_spread_rows_bf16: NULL pointer");
     HGNN_REQUIRE((uintptr_t)table % 16 == 0 && (uintptr_t)out % 16 == 0,
                  "hgnn_spread_rows_bf16: table/out must be 16-byte aligned");
-    const int ncol = F / 8;
-    const int32_t* n_items = plan->counts + HGNN_CNT_WORK;
+    const ItemView v = work_items(plan);
     const unsigned short* t = (const unsigned short*)table;
     unsigned short* o = (unsigned short*)out;
-#define HGNN_S(RL)                                                                                          \
-    do {                                                                                                    \
-        const unsigned grid = (unsigned)ceil_div(plan->max_work, 8);                                        \
-        if (weight)                                                                                         \
-            k_spread_rows_bf16<RL, true, 8><<<grid, 512, 0, stream>>>(t, F, ncol, plan->perm, weight,       \
-                plan->wi_begin, plan->wi_end, plan->wi_dst, n_items, plan->max_work, o);                    \
-        else                                                                                                \
-            k_spread_rows_bf16<RL, false, 8><<<grid, 512, 0, stream>>>(t, F, ncol, plan->perm, weight,      \
-                plan->wi_begin, plan->wi_end, plan->wi_dst, n_items, plan->max_work, o);                    \
-    } while (0)
-    if (ncol <= 4) HGNN_S(4);
-    else if (ncol <= 8) HGNN_S(8);
-    else if (ncol <= 16) HGNN_S(16);
-    else if (ncol <= 32) HGNN_S(32);
-    else HGNN_S(64);
-#undef HGNN_S
+    for_row_shape<64>(F / 8, [&](auto rl, auto) {
+        constexpr int RL = decltype(rl)::value;
+        if (weight)
+            launch_items<8>(k_spread_rows_bf16<RL, true, 8>, v.max_items, stream, t, F, F / 8, v.perm, weight, v.begin,
+                            v.end, v.wi_dst, v.n_items, v.max_items, o);
+        else
+            launch_items<8>(k_spread_rows_bf16<RL, false, 8>, v.max_items, stream, t, F, F / 8, v.perm, weight, v.begin,
+                            v.end, v.wi_dst, v.n_items, v.max_items, o);
+    });
     HGNN_CHECK_HIP(hipGetLastError());
     return HGNN_OK;
 }
@@ -346,23 +330,14 @@ extern "C" int hgnn_gather_rows_bf16(const void* table, int64_t table_rows, int3
     HGNN_REQUIRE(table != nullptr && idx != nullptr && out != nullptr, "hgnn_gather_rows_bf16: NULL pointer");
     HGNN_REQUIRE((uintptr_t)table % 16 == 0 && (uintptr_t)out % 16 == 0,
                  "hgnn_gather_rows_bf16: table/out must be 16-byte aligned");
-    const int ncol = F / 8;
-    int64_t blocks = ceil_div(ceil_div(M, 64), kWavesPerBlock);
-    if (blocks > 8192) blocks = 8192;
-    const unsigned grid = (unsigned)blocks;
+    const unsigned grid = stream_grid(ceil_div(M, 64));
     const unsigned short* t = (const unsigned short*)table;
     unsigned short* o = (unsigned short*)out;
-#define HGNN_G(RL)                                                                                   \
-    do {                                                                                             \
-        if (weight) k_gather_rows_bf16<RL, true><<<grid, 256, 0, stream>>>(t, F, ncol, idx, M, weight, o); \
-        else k_gather_rows_bf16<RL, false><<<grid, 256, 0, stream>>>(t, F, ncol, idx, M, weight, o);  \
-    } while (0)
-    if (ncol <= 4) HGNN_G(4);
-    else if (ncol <= 8) HGNN_G(8);
-    else if (ncol <= 16) HGNN_G(16);
-    else if (ncol <= 32) HGNN_G(32);
-    else HGNN_G(64);
-#undef HGNN_G
+    for_row_shape<64>(F / 8, [&](auto rl, auto) {
+        constexpr int RL = decltype(rl)::value;
+        if (weight) k_gather_rows_bf16<RL, true><<<grid, kBlock, 0, stream>>>(t, F, F / 8, idx, M, weight, o);
+        else k_gather_rows_bf16<RL, false><<<grid, kBlock, 0, stream>>>(t, F, F / 8, idx, M, weight, o);
+    });
     HGNN_CHECK_HIP(hipGetLastError());
     return HGNN_OK;
 }

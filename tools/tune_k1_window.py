@@ -29,11 +29,13 @@ def build_sweep_lib():
     b.build(verbose=False)
     os.makedirs(os.path.dirname(SWEEP_LIB), exist_ok=True)
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    seg = os.path.join(b.CSRC, "segreduce.hip")
-    obj = os.path.join(os.path.dirname(SWEEP_LIB), "segreduce_k1sweep.o")
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", f"--offload-arch={b.ARCH}", "-fPIC", "-DHGNN_K1_SWEEP",
-                           "-c", seg, "-o", obj])
-    objs = [s[:-4] + ".o" for s in b.sources() if s != seg] + [obj]
+    # the variants are in segreduce.hip, the options that pick one in capi.hip
+    sweep = [os.path.join(b.CSRC, n) for n in ("segreduce.hip", "capi.hip")]
+    objs = [s[:-4] + ".o" for s in b.sources() if s not in sweep]
+    for src in sweep:
+        objs.append(os.path.join(os.path.dirname(SWEEP_LIB), os.path.basename(src)[:-4] + "_k1sweep.o"))
+        subprocess.check_call([hipcc, "-O3", "-std=c++17", f"--offload-arch={b.ARCH}", "-fPIC", "-DHGNN_K1_SWEEP",
+                               "-c", src, "-o", objs[-1]])
     subprocess.check_call([hipcc, f"--offload-arch={b.ARCH}", "-shared", "-fPIC", "-o", SWEEP_LIB] + objs)
     return SWEEP_LIB
 
