@@ -9,6 +9,7 @@ Drop-in surface (same names / signatures as the reference):
     eval_metrics(bipartite_graph, event, ...)            <- Modules/tracking_utils.py
     graph_intersection(...), frnn_graph(...)             <- Modules/utils.py (embedding stage)
     bipartite_loss(...), bc_training_loss(...)           <- BipartiteClassificationBase.get_bipartite_loss / training_step
+    hdbscan(points, min_cluster_size), embedding_track_candidates(...)   <- cuml.cluster.HDBSCAN (embedding validation)
 
 Everything on the hot path runs in hand-written HIP kernels loaded from
 libhgnn_hip.so through the C ABI of include/hgnn_hip.h; there is no CPU or
@@ -20,6 +21,9 @@ from .plan import GraphPlan, get_plan, clear_plan_cache, plan_cache_stats  # noq
 from .utils import make_mlp  # noqa: F401
 from .gnn_utils import InteractionGNNCell, HierarchicalGNNCell  # noqa: F401
 from .tracking import eval_metrics, edge_track_candidates, bipartite_track_candidates  # noqa: F401
+from .tracking import embedding_track_candidates  # noqa: F401
+from .hdbscan import hdbscan, hdbscan_tree  # noqa: F401  (the name `hdbscan` is the function; the module is
+#                                             importlib.import_module("hierarchicalgnn_amd.hdbscan"))
 from .embedding import frnn_graph, graph_intersection, training_samples, training_weights, hinge_distance  # noqa: F401
 from .assignment import (max_weight_matching, bipartite_loss, bc_embedding_loss, bc_training_loss,  # noqa: F401
                          gap_bound)

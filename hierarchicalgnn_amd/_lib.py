@@ -32,6 +32,10 @@ AM_SCALE_BITS, AM_FALLBACK_WEIGHT = 30, 1e-12
 AM_ST_BAD_ID, AM_ST_BAD_WEIGHT, AM_ST_OVERFLOW, AM_ST_BUDGET = 1, 2, 4, 8
 AM_N_PAIRS, AM_STATUS, AM_PHASES, AM_GRID_ROUNDS, AM_TAIL_ROUNDS, AM_HOST_READS = range(6)
 AM_INFO = 8
+# HGNN_HDB_*: entries of hgnn_hdbscan_f32's info vector; HGNN_HDBSCAN_LAMBDA_DUP
+(HDB_ROUNDS, HDB_HOST_READS, HDB_N_CLUSTERS, HDB_STAGE_SYNC, HDB_T_CORE_NS, HDB_T_SORT_NS, HDB_T_TREE_NS) = range(7)
+HDB_T_ROUND0_NS, HDB_INFO = 8, 32
+HDBSCAN_LAMBDA_DUP = 2.0 ** 100
 
 class HgnnPlan(Structure):
     """mirror of ``struct hgnn_plan``"""
@@ -135,6 +139,10 @@ _SIGNATURES = {
     "hgnn_assign_match_workspace_bytes": (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     "hgnn_assign_match": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                   c_void_p, c_void_p, POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
+    "hgnn_hdbscan_workspace_bytes": (c_int, [c_int64, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    "hgnn_hdbscan_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
+    "hgnn_hdbscan_tree_host": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, POINTER(c_int64)]),
 }
 
 _lib = None

@@ -11,6 +11,9 @@ cugraph (EdgeClassifier/edge_classifier_base.py:157-168); neither exists on ROCm
                                                    the cut (all edges when none passes), lock-free union-find
     bipartite_track_candidates(bipartite_graph, scores, score_cut, inverse_mask)
                                                    bipartite_classification_base.py:262-263
+    embedding_track_candidates(embeddings, inverse_mask, min_cluster_size)
+                                                   embedding_base.py:267-272: HDBSCAN clusters of the embeddings
+                                                   (hdbscan.py, csrc/hdbscan.hip), noise dropped
 
 There is no CPU path: every input must be a HIP device tensor.
 """
@@ -23,6 +26,7 @@ import torch
 
 from . import _lib
 from .clustering import _cc
+from .hdbscan import hdbscan as _hdbscan
 
 default_response = {
     "track_eff": 0,
@@ -144,3 +148,19 @@ def bipartite_track_candidates(bipartite_graph: torch.Tensor, scores: torch.Tens
         raise RuntimeError("bipartite_track_candidates needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
     g = bipartite_graph[:, scores.reshape(-1) >= score_cut]
     return torch.stack([inverse_mask.to(torch.int64)[g[0]], g[1].to(torch.int64)], dim=0)
+
+
+def embedding_track_candidates(embeddings: torch.Tensor, inverse_mask: torch.Tensor = None,
+                               min_cluster_size: int = 5) -> torch.Tensor:
+    """Track candidates of the embedding models (embedding_base.py:267-272): HDBSCAN clusters of the embeddings
+    (``inference_min_cluster_size``), noise dropped.  Returns the int64 [2, B] graph (hit, cluster label) over the
+    clustered hits in ascending hit position, hit ids mapped through ``inverse_mask`` when it is given; ready for
+    ``eval_metrics``."""
+    if not embeddings.is_cuda:
+        raise RuntimeError("embedding_track_candidates needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
+    clusters = _hdbscan(embeddings.detach().float(), min_cluster_size)
+    hits = torch.nonzero(clusters >= 0).reshape(-1)
+    labels = clusters[hits]
+    if inverse_mask is not None:
+        hits = inverse_mask.to(torch.int64)[hits]
+    return torch.stack([hits, labels], dim=0)

@@ -547,6 +547,52 @@ int hgnn_assign_match(const int64_t* row, const int64_t* col, const float* score
                       int64_t n_cols, int64_t* col_match, int64_t* pair_row, int64_t* pair_col, double* pair_weight,
                       int64_t* info, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Deterministic HDBSCAN* (reference GNNEmbedding/embedding_base.py:40-41,267-272: cuml.cluster.HDBSCAN with
+ * metric='euclidean', cluster_selection_method='eom').  Added under ABI 26: additions only.
+ *
+ * hgnn_hdbscan_f32: points float32 [N, D] (row-major, D <= 16, N <= 2^21).  Definition (DESIGN.md section 3,
+ *   "HDBSCAN"; alpha = 1, cluster_selection_epsilon = 0, no single-cluster result):
+ *     core2[i]  = the min_samples-th smallest squared distance from i, i itself counted (min_samples <= 128);
+ *     w2(i, j)  = max(core2[i], core2[j], d2(i, j)), d2 = the float32 sum of the squared float32 differences in
+ *                 dimension order (one rounded product and one rounded sum per dimension);
+ *     the UNIQUE minimum spanning tree under the strict total order (w2, min(i, j), max(i, j));
+ *     all tree edges of equal w2 are one simultaneous multi-way merge; read top-down a level is a true split iff at
+ *     least two of its parts hold >= min_cluster_size points (the smaller parts fall out of the parent there),
+ *     otherwise the parts below min_cluster_size fall out of the continuing cluster;
+ *     lambda = 1 / sqrt(w2) in float64 (HGNN_HDBSCAN_LAMBDA_DUP for w2 = 0, duplicate points), float64 stabilities,
+ *     EOM: a cluster is selected iff its stability >= the sum of the selected stabilities below it; never the root.
+ *   No tie is broken by arrival order: the partition does not depend on the order of the points.
+ *   Outputs (device): labels int64 [N] (-1 noise; clusters 0..C-1 by smallest member index), mst_edges int64
+ *   [N-1, 2] (min id first) and mst_w2 float32 [N-1] sorted by (w2, min, max), core2 float32 [N].
+ *   info: HOST int64[HGNN_HDB_INFO] or NULL (indices below).  On entry info[HGNN_HDB_STAGE_SYNC] != 0 asks for two
+ *   extra stream synchronisations so that the core-distance and sort stages are timed on their own (measurement
+ *   tools); otherwise the first round's time includes the core distances.  Times are host-clock nanoseconds.
+ *   Like hgnn_assign_match this entry SYNCHRONISES the stream: one read of the edge count per Boruvka round
+ *   (<= 21 rounds), one device-to-host copy of the sorted edges and one host-to-device copy of the labels around
+ *   the sequential tree stage, which is host code; info[HGNN_HDB_HOST_READS] <= 24.  It cannot be captured into a
+ *   graph.  Non-finite coordinates end in HGNN_ERR_INVALID_ARG (a round joins nothing), never in a fault.
+ * hgnn_hdbscan_workspace_bytes: device scratch of one call (any 256-B aligned).
+ * hgnn_hdbscan_tree_host: the tree stage alone, host pointers only (no device is touched): edges int64 [N-1, 2] of
+ *   a spanning tree with w2 [N-1] ascending -> labels [N], *n_clusters (may be NULL).
+ * ------------------------------------------------------------------------ */
+#define HGNN_HDBSCAN_LAMBDA_DUP 0x1p100 /* above 1 / sqrt(smallest positive float32) = 2.7e22 */
+#define HGNN_HDB_ROUNDS 0
+#define HGNN_HDB_HOST_READS 1
+#define HGNN_HDB_N_CLUSTERS 2
+#define HGNN_HDB_STAGE_SYNC 3
+#define HGNN_HDB_T_CORE_NS 4
+#define HGNN_HDB_T_SORT_NS 5   /* sort, edge emission and the copy of the edges to the host */
+#define HGNN_HDB_T_TREE_NS 6   /* the host tree stage alone                                  */
+#define HGNN_HDB_T_ROUND0_NS 8 /* .. + round                                                 */
+#define HGNN_HDB_INFO 32
+int hgnn_hdbscan_workspace_bytes(int64_t N, int32_t D, int32_t min_cluster_size, int32_t min_samples, size_t* bytes);
+int hgnn_hdbscan_f32(const float* points, int64_t N, int32_t D, int32_t min_cluster_size, int32_t min_samples,
+                     int64_t* labels, int64_t* mst_edges, float* mst_w2, float* core2, int64_t* info, void* workspace,
+                     size_t workspace_bytes, hgnn_stream_t stream);
+int hgnn_hdbscan_tree_host(const int64_t* edges, const float* w2, int64_t N, int32_t min_cluster_size,
+                           int64_t* labels, int64_t* n_clusters);
+
 #ifdef __cplusplus
 }
 #endif
