@@ -9,6 +9,7 @@ Drop-in surface (same names / signatures as the reference):
     eval_metrics(bipartite_graph, event, ...)            <- Modules/tracking_utils.py
     graph_intersection(...), frnn_graph(...)             <- Modules/utils.py (embedding stage)
     bipartite_loss(...), bc_training_loss(...)           <- BipartiteClassificationBase.get_bipartite_loss / training_step
+    pair_hinge_loss(...), embedding_hgnn_training_loss(...)   <- EmbeddingBase.training_step's weighted hinge loss
     hdbscan(points, min_cluster_size), embedding_track_candidates(...)   <- cuml.cluster.HDBSCAN (embedding validation)
 
 Everything on the hot path runs in hand-written HIP kernels loaded from
@@ -25,6 +26,8 @@ from .tracking import embedding_track_candidates  # noqa: F401
 from .hdbscan import hdbscan, hdbscan_tree  # noqa: F401  (the name `hdbscan` is the function; the module is
 #                                             importlib.import_module("hierarchicalgnn_amd.hdbscan"))
 from .embedding import frnn_graph, graph_intersection, training_samples, training_weights, hinge_distance  # noqa: F401
+from .embedding import (pair_hinge_loss, pair_hinge_check, embedding_hgnn_training_loss,  # noqa: F401
+                        embedding_in_training_loss)
 from .assignment import (max_weight_matching, bipartite_loss, bc_embedding_loss, bc_training_loss,  # noqa: F401
                          gap_bound)
 

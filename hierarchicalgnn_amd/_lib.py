@@ -36,6 +36,12 @@ AM_INFO = 8
 (HDB_ROUNDS, HDB_HOST_READS, HDB_N_CLUSTERS, HDB_STAGE_SYNC, HDB_T_CORE_NS, HDB_T_SORT_NS, HDB_T_TREE_NS) = range(7)
 HDB_T_ROUND0_NS, HDB_INFO = 8, 32
 HDBSCAN_LAMBDA_DUP = 2.0 ** 100
+# HGNN_PH_*: hgnn_pair_hinge_*'s host hparams vector and device state vector
+PH_MAX_DIM = 16
+(PH_WEIGHT_MIN, PH_WEIGHT_LEAK, PH_PTCUT, PH_PT_INTERVAL, PH_LOG_WEIGHT_RATIO, PH_MARGIN, PH_SCALE) = range(7)
+PH_HPARAMS = 8
+PH_KT, PH_KF, PH_ST, PH_SF, PH_LOSS = range(5)
+PH_STATE = 8
 
 class HgnnPlan(Structure):
     """mirror of ``struct hgnn_plan``"""
@@ -143,6 +149,13 @@ _SIGNATURES = {
     "hgnn_hdbscan_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                  POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
     "hgnn_hdbscan_tree_host": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, POINTER(c_int64)]),
+    "hgnn_pair_hinge_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, POINTER(c_size_t)]),
+    "hgnn_pair_hinge_forward": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64,
+                                        POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                        c_void_p]),
+    "hgnn_pair_hinge_backward": (c_int, [POINTER(HgnnPlan), c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p,
+                                         c_void_p, c_int64, POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -162,13 +162,18 @@ def bipartite_loss(bipartite_scores, bipartite_graph, batch, hparams, return_det
     return asgmt_loss
 
 
-def bc_embedding_loss(embeddings, edge_index, batch, hparams):
+def bc_embedding_loss(embeddings, edge_index, batch, hparams, fused=False):
     """the embedding loss of training_step (:199-204): PID truth on the input edges, get_emb_weight, get_hinge_distance
-    and the squared hinge loss at margin 1 on dist / train_r, dotted with the weights"""
+    and the squared hinge loss at margin 1 on dist / train_r, dotted with the weights.  ``fused=True`` evaluates the
+    same quantity with ``embedding.pair_hinge_loss`` (one HIP operator, no host read, reproducible backward)."""
     if not torch.is_tensor(embeddings) or not embeddings.is_cuda or not edge_index.is_cuda:
         raise RuntimeError("bc_embedding_loss needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
     batch_pid = _field(batch, "pid")
     y_pid = batch_pid[edge_index[0]] == batch_pid[edge_index[1]]
+    if fused:
+        from .embedding import pair_hinge_loss
+        return pair_hinge_loss(embeddings, edge_index, y_pid, batch, hparams, margin=1.0,
+                               scale=1.0 / hparams["train_r"], cache_plan=True)
     weights = training_weights(batch, edge_index, y_pid, hparams)
     hinge, dist = hinge_distance(embeddings, edge_index, y_pid)
     emb_loss = torch.nn.functional.hinge_embedding_loss(dist / hparams["train_r"], hinge, margin=1,

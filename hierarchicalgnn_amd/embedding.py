@@ -12,10 +12,17 @@ fixed-radius kNN graph of the embeddings with knn = 100 (frnn, CUDA-only, there)
     training_samples(embeddings, batch, hparams)     EmbeddingBase.get_training_samples, both true_edges modes
     training_weights(batch, graph, y, hparams)       pt_weighting + get_training_weight (:95-107, :137-146)
     hinge_distance(embeddings, graph, y)             get_hinge_distance (:148-155)
+    pair_hinge_loss(embeddings, graph, y, batch, hparams, margin=None, scale=1.0)
+                                                     the three lines above + hinge_embedding_loss(..)^2 . weights
+                                                     (:167-168) as ONE operator, csrc/pairloss.hip: no [P, emb_dim]
+                                                     tensor, no host read, bitwise reproducible forward and backward
+    embedding_hgnn_training_loss(...) / embedding_in_training_loss(...)
+                                                     training_step after the forward (:160-181 / :191-199)
 
 Differences from the reference, all deliberate: results stay on the input's device (the reference returns CPU
 tensors from graph_intersection and its callers move them), and an empty pred graph gives an empty result (the
-reference raises on ``.max()`` of an empty tensor).  There is no CPU path: inputs must be HIP device tensors.
+reference raises on ``.max()`` of an empty tensor); in ``pair_hinge_loss`` a class of pairs without weight (an empty
+class in particular) contributes nothing where the reference's 0/0 makes the loss NaN.  There is no CPU path: inputs must be HIP device tensors.
 """
 from __future__ import annotations
 
@@ -25,6 +32,7 @@ import torch
 
 from . import _lib
 from .ops import knn_radius
+from .plan import GraphPlan, memo
 
 stats = {"host_reads": 0}
 
@@ -168,3 +176,165 @@ def hinge_distance(embeddings, graph, y):
     hinge[~y] = -1
     dist = ((embeddings[graph[0]] - embeddings[graph[1]]).square().sum(-1) + 1e-12).sqrt()
     return hinge, dist
+
+
+# --------------------------------------------------------------------------- the fused pair hinge loss
+_ph_pending = {}   # device -> int32[1]: the status words of the calls nobody has read yet, OR-ed on the device
+
+
+def _ph_scalars(hparams, margin, scale):
+    h = (ctypes.c_double * _lib.PH_HPARAMS)()
+    h[_lib.PH_WEIGHT_MIN] = float(hparams["weight_min"])
+    h[_lib.PH_WEIGHT_LEAK] = float(hparams["weight_leak"])
+    h[_lib.PH_PTCUT] = float(hparams["ptcut"])
+    h[_lib.PH_PT_INTERVAL] = float(hparams["pt_interval"])
+    h[_lib.PH_LOG_WEIGHT_RATIO] = float(hparams["log_weight_ratio"])
+    h[_lib.PH_MARGIN] = float(hparams["train_r"] if margin is None else margin)
+    h[_lib.PH_SCALE] = float(scale)
+    return h
+
+
+def _ph_workspace(p, n, d, backward, dev):
+    nb = ctypes.c_size_t(0)
+    _lib.check(_lib.load().hgnn_pair_hinge_workspace_bytes(p, n, d, backward, ctypes.byref(nb)),
+               "hgnn_pair_hinge_workspace_bytes")
+    return torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev), int(nb.value)
+
+
+def _ph_plan(graph, n, cache):
+    """the destination-sorted plan over cat(a, b) with the other endpoint as its gather index: every pair sits in the
+    list of both of its endpoints.  Unvalidated (no host read): ids out of range are dropped by the plan build.
+    Costs beside the kernels, per call: the flipped copy of the graph (2P int64), an int64 copy of an int32 graph (the
+    plan build takes int64), and the build itself (a radix sort of 2P keys) -- every step for the training samples,
+    whose pairs change with the embeddings; once per event with ``cache`` (DESIGN.md section 3 "k_ph" has the times)."""
+    g64 = graph if graph.dtype == torch.int64 else graph.long()
+    build = lambda: GraphPlan(g64.reshape(-1), n, g64.flip(0).reshape(-1), n, validate=False)  # noqa: E731
+    if cache and g64 is graph:
+        # kept with the graph tensor (plan.memo), not in the shared plan cache: that cache's key does not tell an
+        # unvalidated plan from a range-checked one
+        return memo(graph, f"pair_hinge_plan/{n}", build)
+    return build()
+
+
+class _PairHinge(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, emb, graph, y8, pt, scalars, cache_plan):
+        lib = _lib.load()
+        dev = emb.device
+        n, d, p = int(emb.shape[0]), int(emb.shape[1]), int(graph.shape[1])
+        idt = _lib.DT_I64 if graph.dtype == torch.int64 else _lib.DT_I32
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        state = torch.empty(_lib.PH_STATE, dtype=torch.float64, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        ws, nb = _ph_workspace(p, n, d, 0, dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.hgnn_pair_hinge_forward(_lib.ptr(emb), n, d, _lib.ptr(graph), idt, _lib.ptr(y8),
+                                                   _lib.ptr(pt), p, scalars, _lib.ptr(loss), _lib.ptr(state),
+                                                   _lib.ptr(status), _lib.ptr(ws), nb, _lib.current_stream(dev)),
+                       "hgnn_pair_hinge_forward")
+        ctx.plan = None
+        if ctx.needs_input_grad[0]:
+            # built once per call, next to the forward; the backward only walks it
+            ctx.plan = _ph_plan(graph, n, cache_plan) if p > 0 and n > 0 else None
+            ctx.save_for_backward(emb, graph, y8, pt, state)
+            ctx.scalars, ctx.idt = scalars, idt
+        ctx.mark_non_differentiable(status)
+        return loss.reshape(()), status
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_status):
+        emb, graph, y8, pt, state = ctx.saved_tensors
+        lib = _lib.load()
+        dev = emb.device
+        n, d, p = int(emb.shape[0]), int(emb.shape[1]), int(graph.shape[1])
+        g = grad_loss.detach().reshape(1).to(torch.float32).contiguous()
+        grad = torch.empty_like(emb)
+        ws, nb = _ph_workspace(p, n, d, 1, dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.hgnn_pair_hinge_backward(ctypes.byref(ctx.plan.c) if ctx.plan is not None else None,
+                                                    _lib.ptr(emb), n, d, _lib.ptr(graph), ctx.idt, _lib.ptr(y8),
+                                                    _lib.ptr(pt), p, ctx.scalars, _lib.ptr(state), _lib.ptr(g),
+                                                    _lib.ptr(grad), _lib.ptr(ws), nb, _lib.current_stream(dev)),
+                       "hgnn_pair_hinge_backward")
+        return grad, None, None, None, None, None
+
+
+def pair_hinge_check(device=None):
+    """Reads (ONE host read per device, counted in ``stats["host_reads"]``) and clears the status words of the
+    ``pair_hinge_loss`` calls made since the last check: ValueError if any of them saw a pair id outside [0, N)."""
+    if device is None:
+        devs = list(_ph_pending)
+    else:
+        dev = torch.device(device)
+        devs = [dev if dev.index is not None else torch.device(dev.type, torch.cuda.current_device())]
+    bad = False
+    for dev in devs:
+        word = _ph_pending.pop(dev, None)
+        if word is not None:
+            stats["host_reads"] += 1
+            bad = bool(word.item()) or bad
+    if bad:
+        raise ValueError("pair_hinge_loss: a pair id is negative or >= the number of embedding rows")
+
+
+def pair_hinge_loss(embeddings, graph, y, batch, hparams, margin=None, scale=1.0, check=False, cache_plan=False):
+    """sum_i w_i l_i^2 (0-d float32, differentiable in ``embeddings`` only) with w = training_weights(batch, graph, y,
+    hparams), d = hinge_distance(embeddings, graph, y), l_i = scale d_i for a true pair and max(0, margin - scale d_i)
+    for a false one: ``hinge_embedding_loss(scale * d, hinge, margin, 'none').square() . w`` of the reference's
+    training steps.  ``margin`` defaults to ``hparams["train_r"]`` (the embedding stage: scale 1, margin train_r;
+    ``bc_embedding_loss``: scale 1 / train_r, margin 1).
+
+    ``embeddings`` float32 [N, D <= 16]; ``graph`` [2, P] int64 or int32; ``y`` [P] bool or uint8; ``batch.pt`` float32
+    [N], not written.  The class sums and the loss are float64 sums in a fixed order and the gradient uses no
+    atomics: two calls return the same bits.  A class of pairs whose weights sum to 0 contributes nothing.
+
+    The call makes NO host read.  A pair id outside [0, N) is skipped by the kernels (never a fault) and recorded in a
+    device status word; ``check=True`` reads it after the call (one host read, counted in ``stats["host_reads"]``) and
+    raises ValueError, as does a later ``pair_hinge_check()``.  ``cache_plan=True`` keeps the backward's plan with the
+    graph tensor (``plan.memo``), for a ``graph`` tensor that is reused from step to step (an event's input edges)."""
+    if not torch.is_tensor(embeddings) or not embeddings.is_cuda or not torch.is_tensor(graph) or not graph.is_cuda:
+        raise RuntimeError("pair_hinge_loss needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
+    dev = embeddings.device
+    if embeddings.dim() != 2 or embeddings.dtype != torch.float32 or not 1 <= embeddings.shape[1] <= _lib.PH_MAX_DIM:
+        raise ValueError(f"pair_hinge_loss: embeddings must be float32 [N, D <= {_lib.PH_MAX_DIM}], got "
+                         f"{embeddings.dtype} {tuple(embeddings.shape)}")
+    if graph.dim() != 2 or graph.shape[0] != 2 or graph.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"pair_hinge_loss: graph must be int64 or int32 [2, P], got {graph.dtype} {tuple(graph.shape)}")
+    if not torch.is_tensor(y) or y.dtype not in (torch.bool, torch.uint8) or y.shape != (graph.shape[1],):
+        raise ValueError("pair_hinge_loss: y must be bool or uint8 with one entry per pair")
+    pt = _field(batch, "pt")
+    if pt.dtype != torch.float32 or pt.numel() != embeddings.shape[0]:
+        raise ValueError("pair_hinge_loss: batch.pt must be float32 with one entry per embedding row")
+    if graph.device != dev or y.device != dev or pt.device != dev:
+        raise ValueError("pair_hinge_loss: embeddings, graph, y and batch.pt must be on one device")
+    y8 = y.contiguous().view(torch.uint8)
+    loss, status = _PairHinge.apply(embeddings.contiguous(), graph.contiguous(), y8, pt.detach().reshape(-1).contiguous(),
+                                    _ph_scalars(hparams, margin, scale), bool(cache_plan))
+    word = _ph_pending.get(dev)
+    _ph_pending[dev] = status if word is None else word | status
+    if check:
+        pair_hinge_check(dev)
+    return loss
+
+
+def embedding_in_training_loss(embeddings, batch, hparams, prediction_graph=None):
+    """EmbeddingBase.training_step for Embedding-IN after the forward (embedding_base.py:191-199)"""
+    graph, y = training_samples(embeddings, batch, hparams, prediction_graph)
+    return pair_hinge_loss(embeddings, graph, y, batch, hparams)
+
+
+def embedding_hgnn_training_loss(embeddings, intermediate_embeddings, batch, hparams, loss_schedule,
+                                 prediction_graph=None):
+    """EmbeddingBase.training_step for Embedding-HGNN-GMM after the forward (embedding_base.py:160-181):
+    (loss, emb_loss, intermediate_loss) with loss = loss_schedule * intermediate_loss + (1 - loss_schedule) * emb_loss.
+    The intermediate term is the PID truth on ``batch.edge_index`` with the intermediate embeddings, the second term
+    ``training_samples`` with the final ones.  ``loss_schedule`` is the caller's (the reference takes it from hparams
+    or from the epoch, :177-180)."""
+    edge_index = _field(batch, "edge_index")
+    pid = _field(batch, "pid")
+    y_pid = pid[edge_index[0]] == pid[edge_index[1]]
+    intermediate_loss = pair_hinge_loss(intermediate_embeddings, edge_index, y_pid, batch, hparams, cache_plan=True)
+    graph, y = training_samples(embeddings, batch, hparams, prediction_graph)
+    emb_loss = pair_hinge_loss(embeddings, graph, y, batch, hparams)
+    loss = (loss_schedule * intermediate_loss) + ((1 - loss_schedule) * emb_loss)
+    return loss, emb_loss, intermediate_loss

@@ -6,6 +6,9 @@ for a plain training loop).
     InteractionGNNBlock  <- EdgeClassifier/Models/IN.py:15-95
     EC_InteractionGNN    <- EdgeClassifier/Models/IN.py:97-128
     Embedding_InteractionGNN <- GNNEmbedding/Models/IN.py:99-118
+    BC_MessagePassing    <- BipartiteClassification/Models/HGNN_GMM.py:300-346
+    Embedding_HierarchicalGNN_GMM <- GNNEmbedding/Models/HGNN_GMM.py:278-301
+    gMRT                 <- gMRT/Models/HGNN_GMM.py:276-356
 
 Sub-module names (``ignn_block.node_encoder``, ``ignn_block.edge_encoder``,
 ``ignn_block.ignn_cells.{i}``, ``edge_classifier``) and therefore the
@@ -22,7 +25,7 @@ import torch.nn as nn
 from .gnn_utils import InteractionGNNCell, _maybe_checkpoint
 from .mlp import concat_mlp
 from .plan import memo, stable_index
-from .utils import make_mlp, process_hparams
+from .utils import make_mlp, match_dims, process_hparams
 
 
 def _bf16_features(hparams) -> bool:
@@ -189,9 +192,13 @@ class HierarchicalGNNBlock(nn.Module):
     (centroids ``means``, bipartite and super graphs with their weights) as inputs.
     Sub-module names match the reference, so its ``hgnn_block.*`` weights load
     (the graph-construction buffers it also holds are simply not used here).
+
+    The embedding stage's block (GNNEmbedding/Models/HGNN_GMM.py:99-276) is the same block with two switches:
+    ``l1_pool=False`` pools the node rows as they are (:256, no L1 row normalisation) and ``emb_head=True`` gives the
+    block the ``output_layer`` (:149-157) whose normalised output is the model's final embedding (``embed_head``).
     """
 
-    def __init__(self, hparams):
+    def __init__(self, hparams, l1_pool=True, emb_head=False):
         super().__init__()
         from .gnn_utils import HierarchicalGNNCell
         hparams = process_hparams(hparams)
@@ -209,6 +216,11 @@ class HierarchicalGNNBlock(nn.Module):
         else:
             cells = [HierarchicalGNNCell(hparams) for _ in range(n)]
         self.hgnn_cells = nn.ModuleList(cells)
+        if emb_head:
+            self.output_layer = make_mlp(hparams["latent"], hparams["hidden"], hparams["emb_dim"],
+                                         hparams["output_layers"], layer_norm=ln, output_activation=None,
+                                         hidden_activation=hparams["hidden_output_activation"])
+        self.l1_pool, self.emb_head = bool(l1_pool), bool(emb_head)
         # same names / buffers as the reference block (HGNN_GMM.py:155-157) so that its
         # state_dict loads strictly; `score_cut` belongs to the (host-side) GMM edge cut
         from .graph_construction import DynamicGraphConstruction
@@ -263,9 +275,10 @@ class HierarchicalGNNBlock(nn.Module):
                 super_edge_weights):
         from .ops import gather_scale_scatter, l1_row_scale
         graph, bipartite_graph, super_graph = (stable_index(g) for g in (graph, bipartite_graph, super_graph))
-        # HGNN_GMM.py:269 -- L1-normalised rows, weighted, summed per supernode (K5, one fused kernel)
+        # HGNN_GMM.py:269 -- L1-normalised rows, weighted, summed per supernode (K5, one fused kernel); the embedding
+        # stage's block pools the rows as they are (GNNEmbedding/Models/HGNN_GMM.py:256)
         pooled = gather_scale_scatter(nodes, bipartite_graph[0], bipartite_graph[1], means.shape[0],
-                                      bipartite_edge_weights, row_scale=l1_row_scale(nodes))
+                                      bipartite_edge_weights, row_scale=l1_row_scale(nodes) if self.l1_pool else None)
         supernodes = torch.cat([means.to(nodes.dtype),
                                 _maybe_checkpoint(self._ckpt, self._encode_supernodes, pooled)], dim=-1)
         superedges = _maybe_checkpoint(self._ckpt, self._encode_superedges, supernodes, super_graph)
@@ -274,6 +287,22 @@ class HierarchicalGNNBlock(nn.Module):
                                                         bipartite_graph, bipartite_edge_weights,
                                                         super_graph, super_edge_weights)
         return nodes, supernodes, edges, superedges
+
+    def embed_head(self, nodes):
+        """GNNEmbedding/Models/HGNN_GMM.py:273-274: the final unit embeddings from the block's node rows"""
+        return nn.functional.normalize(concat_mlp(self.output_layer, [(nodes.float(), None)]))
+
+    def decide(self, embeddings, directed_graph, hierarchy=None):
+        """(clusters, means, bipartite graph, its weights, super graph, its weights): the GPU hierarchy decision, or
+        -- ``hierarchy`` = (clusters, bipartite_graph, super_graph) -- a caller's topology with only the differentiable
+        attention weights evaluated on it"""
+        if hierarchy is None:
+            clusters, n_clusters = self.clustering(embeddings, directed_graph, return_count=True)
+            means, bg, bw, sg, sw, _ = self.hierarchy_from_clusters(embeddings, clusters, n_clusters)
+        else:
+            clusters, bg, sg = hierarchy
+            means, bg, bw, sg, sw, _ = self.hierarchy_from_clusters(embeddings, clusters, graphs=(bg, sg))
+        return clusters, means, bg, bw, sg, sw
 
 
 class BC_MessagePassing(nn.Module):
@@ -319,6 +348,89 @@ class BC_MessagePassing(nn.Module):
                        [(_head_input(nodes, self.hparams), bipartite_graph[0]),
                         (_head_input(supernodes, self.hparams), bipartite_graph[1])]).squeeze(-1)
         return torch.sigmoid(s.float())
+
+
+class Embedding_HierarchicalGNN_GMM(nn.Module):
+    """GNNEmbedding/Models/HGNN_GMM.py:278-301 without its Lightning base: IGNN block (intermediate embeddings) ->
+    hierarchy decision on them -> HGNN block without the L1 pooling normalisation -> the block's own embedding head.
+    ``forward(x, graph)`` returns (embeddings, intermediate_embeddings, clusters).  Runs on the destination-sorted
+    layout without the un-permute, as BC_MessagePassing does.  The training step's loss is
+    ``embedding.embedding_hgnn_training_loss``."""
+
+    def __init__(self, hparams):
+        super().__init__()
+        hparams = process_hparams(hparams)
+        self.hparams = hparams
+        self.ignn_block = InteractionGNNBlock(hparams, hparams["n_interaction_graph_iters"], emb=True)
+        self.hgnn_block = HierarchicalGNNBlock(hparams, l1_pool=False, emb_head=True)
+        _mark_split3(self, hparams)
+
+    def forward(self, x, graph, hierarchy=None):
+        """``hierarchy`` = (clusters, bipartite_graph, super_graph) replaces the GPU hierarchy decision"""
+        graph = stable_index(graph)
+        directed_graph = memo(graph, "directed", lambda: torch.cat([graph, graph.flip(0)], dim=1))   # :295
+        intermediate, nodes, edges, directed_graph, _ = self.ignn_block.run(x, directed_graph, restore_order=False)
+        clusters, means, bg, bw, sg, sw = self.hgnn_block.decide(intermediate, directed_graph, hierarchy)
+        nodes, _, _, _ = self.hgnn_block(nodes, edges, directed_graph, means, bg, bw, sg, sw)
+        return self.hgnn_block.embed_head(nodes), intermediate, clusters
+
+
+class gMRT(nn.Module):
+    """gMRT/Models/HGNN_GMM.py:276-356 without its Lightning base: one-layer ``match_dims`` encoders and embedding
+    head instead of an IGNN block, then the BC-style HGNN block (L1 pooling, :243-250) and the bipartite head.
+    ``forward(x, graph)`` returns (bipartite_graph, bipartite_scores, embeddings); the training loss is
+    ``assignment.bc_training_loss``.  The config keys ``data_dir`` / ``super_dir`` (the reference's supergraph dump
+    directories) are accepted and ignored."""
+
+    def __init__(self, hparams):
+        super().__init__()
+        hparams = process_hparams(hparams)
+        self.hparams = hparams
+        act, ln = hparams["hidden_activation"], hparams["layernorm"]
+        self.node_encoder = match_dims(hparams["spatial_channels"], hparams["latent"], layer_norm=ln,
+                                       output_activation=act)
+        self.edge_encoder = match_dims(2 * hparams["spatial_channels"], hparams["latent"], layer_norm=ln,
+                                       output_activation=act)
+        self.output_layer = match_dims(hparams["latent"], hparams["emb_dim"], layer_norm=ln, output_activation=None)
+        self.hgnn_block = HierarchicalGNNBlock(hparams)
+        self.bipartite_output_layer = make_mlp(2 * hparams["latent"], hparams["hidden"], 1,
+                                               hparams["output_layers"], layer_norm=ln, output_activation=None,
+                                               hidden_activation=hparams["hidden_output_activation"])
+        self._ckpt = bool(hparams.get("checkpointing", True))
+        _mark_split3(self, hparams)
+
+    def _encode_nodes(self, x):
+        return concat_mlp(self.node_encoder, [(x, None)], bf16_tail=_bf16_features(self.hparams))
+
+    def _encode_edges(self, x, graph):
+        return concat_mlp(self.edge_encoder, [(x, graph[0]), (x, graph[1])], bf16_tail=_bf16_features(self.hparams))
+
+    def embed(self, x, graph):
+        """:339-344: (directed_graph, embeddings, nodes, edges) on the destination-sorted layout.  Like the reference
+        (:337) and ``InteractionGNNBlock.run`` it sets ``requires_grad`` on the CALLER's leaf ``x`` when autograd
+        records (the reentrant checkpoints need an input with a gradient): the caller's tensor is changed, and the
+        backward computes a gradient for ``x`` that a training step never uses."""
+        if torch.is_grad_enabled() and x.is_leaf and not x.requires_grad:
+            x.requires_grad = True                                                               # :337
+        graph = stable_index(graph)
+        directed_graph = memo(graph, "directed", lambda: torch.cat([graph, graph.flip(0)], dim=1))
+        if self.hparams.get("sort_edges", True) and directed_graph.is_cuda and directed_graph.shape[1] > 0:
+            _, directed_graph, _ = memo(directed_graph, "dst_sorted", lambda g=directed_graph: _dst_sorted(g))
+        nodes = _maybe_checkpoint(self._ckpt, self._encode_nodes, x)
+        edges = _maybe_checkpoint(self._ckpt, self._encode_edges, x, directed_graph)
+        emb = nn.functional.normalize(concat_mlp(self.output_layer, [(nodes.float(), None)]))
+        if _bf16_features(self.hparams):
+            nodes, edges = nodes.bfloat16(), edges.bfloat16()
+        return directed_graph, emb, nodes, edges
+
+    def forward(self, x, graph, hierarchy=None):
+        """``hierarchy`` = (clusters, bipartite_graph, super_graph) replaces the GPU hierarchy decision"""
+        directed_graph, emb, nodes, edges = self.embed(x, graph)
+        _, means, bg, bw, sg, sw = self.hgnn_block.decide(emb, directed_graph, hierarchy)
+        nodes, supernodes, _, _ = self.hgnn_block(nodes, edges, directed_graph, means, bg, bw, sg, sw)
+        return bg, self.score(nodes, supernodes, bg), emb
+
+    score = BC_MessagePassing.score
 
 
 class GraphedInference:

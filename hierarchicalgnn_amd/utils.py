@@ -1,5 +1,5 @@
-"""Host-side mirror of the one helper of the reference's Modules/utils.py that is
-on the hot path: ``make_mlp`` (utils.py:169-196).
+"""Host-side mirror of the helpers of the reference's Modules/utils.py that are
+on the hot path: ``make_mlp`` (utils.py:169-196) and ``match_dims`` (utils.py:209-225).
 
 It builds the same ``nn.Sequential`` (same sub-module indices, hence the same
 ``state_dict`` keys: ``{0,3,6}.weight`` Linear, ``{1,4,7}.weight`` LayerNorm
@@ -57,6 +57,17 @@ def make_mlp(input_size, hidden_size, output_size, hidden_layers, hidden_activat
         if layer_norm:
             layers.append(nn.LayerNorm(sizes[-1]))
         layers.append(out_act())
+    return FusedMLPSequential(*layers)
+
+
+def match_dims(input_size, output_size, output_activation="GELU", layer_norm=False):
+    """Modules/utils.py:209-225: Linear -> (LayerNorm) -> (act), the one-layer encoders of the gMRT model; same
+    sub-module indices as the reference's nn.Sequential"""
+    layers = [nn.Linear(input_size, output_size)]
+    if layer_norm:
+        layers.append(nn.LayerNorm(output_size))
+    if output_activation is not None:
+        layers.append(getattr(nn, output_activation)())
     return FusedMLPSequential(*layers)
 
 

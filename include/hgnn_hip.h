@@ -593,6 +593,58 @@ int hgnn_hdbscan_f32(const float* points, int64_t N, int32_t D, int32_t min_clus
 int hgnn_hdbscan_tree_host(const int64_t* edges, const float* w2, int64_t N, int32_t min_cluster_size,
                            int64_t* labels, int64_t* n_clusters);
 
+/* ------------------------------------------------------------------------
+ * Weighted squared pair hinge loss of the embedding stage (reference GNNEmbedding/embedding_base.py:95-107,
+ * :137-155, :167-168: pt_weighting + get_training_weight + get_hinge_distance + hinge_embedding_loss(..)^2 . weights,
+ * a few dozen elementwise library kernels and several host reads there).  Added under ABI 26: additions only.
+ *
+ * E float32 [N, D] (1 <= D <= HGNN_PH_MAX_DIM), graph [2, P] pair ids (row a, then row b; int32 or int64 by
+ * index_dtype = HGNN_DT_I32 / HGNN_DT_I64), y uint8 [P] (!= 0 = true pair), pt float32 [N]; hparams: HOST
+ * double[HGNN_PH_HPARAMS] (indices below), read before the call returns.  Definition ("k_ph"):
+ *     ptw(p) = pt_weighting(p), NaN read as 0, in float32;   raw_i = ptw(pt[a_i]) + ptw(pt[b_i])
+ *     S_T = sum_{y_i} raw_i,  S_F = sum_{!y_i} raw_i
+ *     w_i = raw_i / S_T * sigmoid(lwr) if y_i, else raw_i / S_F * sigmoid(-lwr)
+ *     d_i = sqrt(|E[a_i] - E[b_i]|^2 + 1e-12) (float32),  l_i = y_i ? scale d_i : max(0, margin - scale d_i)
+ *     loss = sum_i w_i l_i^2
+ *   A class whose weights sum to 0 -- an empty class in particular -- contributes nothing (the reference divides 0 by
+ *   0 there and returns NaN); P = 0 gives 0.  S_T, S_F and the loss are float64 sums in a fixed order that depends on
+ *   P alone: two calls give the same bits, and a permutation of the pairs changes the loss by float64 rounding only.
+ * hgnn_pair_hinge_forward: loss device float[1]; state device double[HGNN_PH_STATE] (what the backward needs, and the
+ *   loss and the class sums in float64); status device int32[1], cleared first: 1 = an endpoint outside [0, N) (such
+ *   pairs are skipped, never a fault).
+ * hgnn_pair_hinge_backward: grad_E [N, D] (every element written) = grad_out[0] * d loss / d E, the only gradient;
+ *   grad_out device float[1]; state as the forward wrote it; plan: the built gather plan with dst_index = cat(a, b),
+ *   gather_index = cat(b, a) (int64 [2P]), n_dst = n_src = N -- it may be built before the forward and reused.  Each
+ *   row is the sum of its list in the plan's order (stable by position), formed as c_i (E[v] - E[other]): no atomics,
+ *   the same bits for every launch shape and plan chunk.
+ * Both launch asynchronously, allocate nothing and never synchronise.
+ * hgnn_pair_hinge_workspace_bytes: device scratch of one forward (backward = 0) or backward (1) call (256-B aligned).
+ * ------------------------------------------------------------------------ */
+#define HGNN_PH_MAX_DIM 16
+#define HGNN_PH_WEIGHT_MIN 0
+#define HGNN_PH_WEIGHT_LEAK 1
+#define HGNN_PH_PTCUT 2
+#define HGNN_PH_PT_INTERVAL 3
+#define HGNN_PH_LOG_WEIGHT_RATIO 4
+#define HGNN_PH_MARGIN 5
+#define HGNN_PH_SCALE 6
+#define HGNN_PH_HPARAMS 8
+#define HGNN_PH_KT 0     /* sigmoid(lwr) / S_T, 0 for a class without weight */
+#define HGNN_PH_KF 1     /* sigmoid(-lwr) / S_F                               */
+#define HGNN_PH_ST 2
+#define HGNN_PH_SF 3
+#define HGNN_PH_LOSS 4   /* the loss before it is rounded to float32          */
+#define HGNN_PH_STATE 8
+int hgnn_pair_hinge_workspace_bytes(int64_t P, int64_t N, int32_t D, int32_t backward, size_t* bytes);
+int hgnn_pair_hinge_forward(const float* E, int64_t N, int32_t D, const void* graph, int32_t index_dtype,
+                            const uint8_t* y, const float* pt, int64_t P, const double* hparams, float* loss,
+                            double* state, int32_t* status, void* workspace, size_t workspace_bytes,
+                            hgnn_stream_t stream);
+int hgnn_pair_hinge_backward(const hgnn_plan* plan, const float* E, int64_t N, int32_t D, const void* graph,
+                             int32_t index_dtype, const uint8_t* y, const float* pt, int64_t P, const double* hparams,
+                             const double* state, const float* grad_out, float* grad_E, void* workspace,
+                             size_t workspace_bytes, hgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
