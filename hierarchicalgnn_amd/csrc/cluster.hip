@@ -195,8 +195,9 @@ __global__ __launch_bounds__(kGmmThreads) void k_gmm_pass(const float* __restric
                 const double eps10 = 10.0 * 1.1920928955078125e-07;  // sklearn: nk += 10 * eps(float32 data)
                 const double n0 = s[0] + eps10, n1 = s[3] + eps10;
                 const double m0 = s[1] / n0, m1 = s[4] / n1;
-                state[S_W0] = n0 / (double)M;
-                state[S_W1] = n1 / (double)M;
+                // sklearn normalises the weights after adding 10 eps to each nk: they sum to 1 for any M
+                state[S_W0] = n0 / (n0 + n1);
+                state[S_W1] = n1 / (n0 + n1);
                 state[S_MU0] = m0;
                 state[S_MU1] = m1;
                 state[S_VAR0] = fmax(s[2] / n0 - m0 * m0, 0.0) + (double)reg_covar;
@@ -321,7 +322,9 @@ extern "C" int hgnn_gmm2_fit_f32(const float* v, int64_t M, int32_t max_iter, fl
     hipStream_t stream = (hipStream_t)stream_;
     HGNN_REQUIRE(M > 0 && v != nullptr && state != nullptr && partials != nullptr && ticket != nullptr,
                  "hgnn_gmm2_fit_f32: NULL argument or empty input");
-    HGNN_REQUIRE(max_iter >= 1 && max_iter <= 1000 && tol >= 0.f && reg_covar >= 0.f, "hgnn_gmm2_fit_f32: bad parameters");
+    HGNN_REQUIRE(max_iter >= 1 && max_iter <= 1000 && tol >= 0.f, "hgnn_gmm2_fit_f32: bad parameters");
+    // a component of identical values has variance exactly reg_covar, and the E step divides by it
+    HGNN_REQUIRE(reg_covar > 0.f, "hgnn_gmm2_fit_f32: reg_covar must be positive (got %g)", (double)reg_covar);
     int64_t want = ceil_div(M, (int64_t)kGmmThreads * 4);
     const unsigned grid = (unsigned)(want < 1 ? 1 : (want > kGmmBlocks ? kGmmBlocks : want));
     k_gmm_reset<<<1, 64, 0, stream>>>(state, ticket);
@@ -350,7 +353,8 @@ extern "C" int hgnn_cc_labels(const int64_t* src, const int64_t* dst, int64_t M,
     if (n == 0) return HGNN_OK;
     HGNN_REQUIRE(labels != nullptr && present != nullptr && (M == 0 || (src != nullptr && dst != nullptr)),
                  "hgnn_cc_labels: NULL argument");
-    HGNN_REQUIRE((score == nullptr) == (cut == nullptr), "hgnn_cc_labels: score and cut go together");
+    // an empty edge list has no score array to point at
+    HGNN_REQUIRE(M == 0 || (score == nullptr) == (cut == nullptr), "hgnn_cc_labels: score and cut go together");
     k_cc_init<<<(unsigned)ceil_div(n, 256), 256, 0, stream>>>(labels, present, n);
     if (M > 0) k_cc_hook<<<(unsigned)ceil_div(M, 256), 256, 0, stream>>>(src, dst, M, n, score, cut, labels, present);
     k_cc_compress<<<(unsigned)ceil_div(n, 256), 256, 0, stream>>>(labels, n);

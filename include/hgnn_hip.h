@@ -245,7 +245,10 @@ int hgnn_knn_radius_ws_f32(const float* query, int64_t nq, const float* points, 
  *   the reference gets from sklearn GaussianMixture(2).fit on the CPU (:192).  Deterministic 2-means start
  *   from the data extremes, then at most max_iter EM passes with sklearn's stopping rule (change of the mean
  *   log-likelihood < tol; reg_covar added to the variances) evaluated ON THE DEVICE: all passes are enqueued,
- *   the ones after convergence return immediately.  state: double[HGNN_GMM_STATE] =
+ *   the ones after convergence return immediately.  As in sklearn, n_k += 10 eps(float32) and the weights are
+ *   n_k / (n_0 + n_1): they sum to 1 for any M.  M >= 1, 1 <= max_iter <= 1000, tol >= 0 and reg_covar > 0
+ *   (a component of identical values has variance exactly reg_covar, and the E step divides by it; 0 is
+ *   refused with HGNN_ERR_INVALID_ARG).  state: double[HGNN_GMM_STATE] =
  *   {w0, w1, mu0, mu1, var0, var1, previous lower bound, converged, EM passes run, min, max, c0, c1, cut,
  *    last lower bound, -};  partials: double[HGNN_GMM_BLOCKS * 8] scratch;  ticket: one uint32 scratch.
  * hgnn_gmm2_cut_f32: the cut x between the two means where sigmoid(r) P(left|x) = sigmoid(-r) P(right|x)
@@ -255,8 +258,10 @@ int hgnn_knn_radius_ws_f32(const float* query, int64_t nq, const float* points, 
  * hgnn_cc_labels: weakly connected components over vertices 0..n-1 of the edges (src[e], dst[e]) whose
  *   score[e] >= *cut (score == cut == NULL: all edges), :212-221 (cugraph in the reference).  labels[v] =
  *   smallest vertex id of v's component (v itself if isolated); present[v] = 1 iff v is an endpoint of a
- *   kept edge.  Lock-free union-find: one pass over the edges, one compression pass; no iteration to
- *   convergence and therefore no host read.
+ *   kept edge.  Edges with a NaN score or an endpoint outside [0, n) are dropped.  score and cut are given
+ *   together or not at all; with M = 0 (src, dst and score may be NULL) a cut alone is accepted and every
+ *   vertex is its own component.  Lock-free union-find: one pass over the edges, one compression pass; no
+ *   iteration to convergence and therefore no host read.
  * ------------------------------------------------------------------------ */
 #define HGNN_GMM_STATE 16
 #define HGNN_GMM_BLOCKS 1024
