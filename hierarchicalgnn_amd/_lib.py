@@ -78,6 +78,7 @@ _SIGNATURES = {
     "hgnn_abi_version": (c_int, []),
     "hgnn_last_error": (c_char_p, []),
     "hgnn_set_option": (c_int, [c_char_p, c_int]),
+    "hgnn_get_option": (c_int, [c_char_p, POINTER(c_int)]),
     "hgnn_sizeof_plan": (c_int, []),
     "hgnn_sizeof_mlp_desc": (c_int, []),
     "hgnn_plan_dims": (c_int, [c_int64, c_int64, c_int64, c_int32, POINTER(HgnnPlan)]),
@@ -85,6 +86,10 @@ _SIGNATURES = {
     "hgnn_plan_build": (c_int, [c_void_p, c_void_p, POINTER(HgnnPlan), c_void_p, c_size_t, c_void_p]),
     "hgnn_segment_reduce_f32": (c_int, [POINTER(HgnnPlan), c_void_p, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+    "hgnn_segment_reduce_f32_ex": (c_int, [POINTER(HgnnPlan), c_void_p, c_int32, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hgnn_plan_item_order_workspace_bytes": (c_int, [POINTER(HgnnPlan), POINTER(c_size_t)]),
+    "hgnn_plan_item_order": (c_int, [POINTER(HgnnPlan), c_void_p, c_void_p, c_size_t, c_void_p]),
     "hgnn_segment_reduce_ex": (c_int, [POINTER(HgnnPlan), c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "hgnn_segment_arg_backward": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -197,6 +202,12 @@ def check(rc: int, what: str = "") -> None:
     if rc != HGNN_OK:
         msg = load().hgnn_last_error()
         raise RuntimeError(f"libhgnn_hip {what} failed (status {rc}): {msg.decode() if msg else ''}")
+
+
+def get_option(name: str) -> int:
+    v = c_int(0)
+    check(load().hgnn_get_option(name.encode(), byref(v)), "hgnn_get_option")
+    return v.value
 
 
 def ptr(t):

@@ -23,6 +23,8 @@ static const struct {
 } kOptions[] = {
     {"nt_loads", &g_opt_nt_loads, INT_MIN, INT_MAX, nullptr},
     {"nt_stores", &g_opt_nt_stores, INT_MIN, INT_MAX, nullptr},
+    {"k1_one_launch", &g_opt_k1_one_launch, 0, 1, "takes 0 or 1"},
+    {"k1_item_order", &g_opt_k1_item_order, 0, 1, "takes 0 or 1"},
 #ifdef HGNN_K1_SWEEP
     {"k1_window", &g_opt_k1_window, INT_MIN, INT_MAX, nullptr},
     {"k1_waves", &g_opt_k1_waves, INT_MIN, INT_MAX, nullptr},
@@ -57,5 +59,16 @@ extern "C" int hgnn_set_option(const char* name, int value) {
         return HGNN_OK;
     }
     set_error("hgnn_set_option: unknown option '%s'", name);
+    return HGNN_ERR_INVALID_ARG;
+}
+
+extern "C" int hgnn_get_option(const char* name, int* value) {
+    HGNN_REQUIRE(name != nullptr && value != nullptr, "hgnn_get_option: NULL pointer");
+    for (const auto& o : kOptions) {
+        if (strcmp(name, o.name)) continue;
+        *value = *o.value;
+        return HGNN_OK;
+    }
+    set_error("hgnn_get_option: unknown option '%s'", name);
     return HGNN_ERR_INVALID_ARG;
 }

@@ -6,6 +6,8 @@ namespace hgnn {
 
 extern int g_opt_nt_loads;   // segreduce.hip
 extern int g_opt_nt_stores;  // segreduce.hip
+extern int g_opt_k1_one_launch;  // segreduce.hip
+extern int g_opt_k1_item_order;  // segreduce.hip
 #ifdef HGNN_K1_SWEEP         // the sweep library of tools/tune_k1_window.py only
 extern int g_opt_k1_window;  // segreduce.hip
 extern int g_opt_k1_waves;   // segreduce.hip

@@ -131,6 +131,22 @@ __global__ __launch_bounds__(256) void k_index_to_i32(const int64_t* __restrict_
     if (!ok && err != nullptr) atomicOr(err, 1);
 }
 
+// Sort key of slot i for the longest-first item order: lists in buckets of 8 rows, longest bucket first, slots
+// past the count last.  The sort is stable, so neighbouring destinations of one bucket stay neighbours (and go on
+// sharing index cache lines) and a slot past the count keeps an index past the count.
+__global__ __launch_bounds__(256) void k_plan_order_keys(hgnn_plan plan, int32_t top, int32_t* __restrict__ keys,
+                                                         int32_t* __restrict__ vals) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= plan.max_work) return;
+    int32_t key = top + 1;
+    if (i < plan.counts[HGNN_CNT_WORK]) {
+        const int32_t bucket = (plan.wi_end[i] - plan.wi_begin[i]) >> 3;
+        key = top - (bucket < top ? bucket : top);
+    }
+    keys[i] = key;
+    vals[i] = (int32_t)i;
+}
+
 static int key_bits(int64_t N) {
     int bits = 1;
     while (bits < 31 && ((int64_t)1 << bits) <= N) ++bits;  // keys are in [0, N]
@@ -170,9 +186,74 @@ static int plan_scratch_layout(int64_t M, int64_t N, PlanScratch* s, hipStream_t
     return HGNN_OK;
 }
 
+struct OrderScratch {
+    size_t keys_in, keys_out, vals_in, temp, temp_bytes, total;
+    int32_t top;  // bucket of the longest list a plan can hold
+};
+
+static int order_scratch_layout(const hgnn_plan* plan, OrderScratch* s, hipStream_t stream) {
+    const size_t n = (size_t)plan->max_work;
+    // a list that is not split has at most chunk rows, a chunk of a split one at most chunk as well
+    s->top = plan->chunk >> 3;
+    s->temp_bytes = 0;
+    if (n > 0)
+        HGNN_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, s->temp_bytes, (int32_t*)nullptr, (int32_t*)nullptr,
+                                                 (int32_t*)nullptr, (int32_t*)nullptr, n, 0u,
+                                                 (unsigned)key_bits(s->top + 1), stream));
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    s->keys_in = take(n * 4);
+    s->keys_out = take(n * 4);
+    s->vals_in = take(n * 4);
+    s->temp = take(s->temp_bytes + 256);
+    s->total = off;
+    return HGNN_OK;
+}
+
 }  // namespace hgnn
 
 using namespace hgnn;
+
+extern "C" int hgnn_plan_item_order_workspace_bytes(const hgnn_plan* plan, size_t* bytes) {
+    HGNN_REQUIRE(plan != nullptr && bytes != nullptr, "hgnn_plan_item_order_workspace_bytes: NULL pointer");
+    HGNN_REQUIRE(plan->chunk > 0 && plan->max_work >= 0, "hgnn_plan_item_order_workspace_bytes: plan dims not initialised");
+    OrderScratch s;
+    int rc = order_scratch_layout(plan, &s, nullptr);
+    if (rc != HGNN_OK) return rc;
+    *bytes = s.total;
+    return HGNN_OK;
+}
+
+extern "C" int hgnn_plan_item_order(const hgnn_plan* plan, int32_t* order, void* workspace, size_t workspace_bytes,
+                                    hgnn_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    HGNN_REQUIRE(plan != nullptr, "hgnn_plan_item_order: plan is NULL");
+    HGNN_REQUIRE(plan->chunk > 0 && plan->max_work >= 0, "hgnn_plan_item_order: plan dims not initialised");
+    if (plan->max_work == 0) return HGNN_OK;
+    HGNN_REQUIRE(order != nullptr, "hgnn_plan_item_order: order is NULL");
+    HGNN_REQUIRE(plan->counts && plan->wi_begin && plan->wi_end, "hgnn_plan_item_order: a plan array pointer is NULL");
+    OrderScratch s;
+    int rc = order_scratch_layout(plan, &s, stream);
+    if (rc != HGNN_OK) return rc;
+    if (workspace_bytes < s.total || workspace == nullptr) {
+        set_error("hgnn_plan_item_order: workspace too small (%zu < %zu)", workspace_bytes, s.total);
+        return HGNN_ERR_WORKSPACE;
+    }
+    char* ws = (char*)workspace;
+    int32_t* keys_in = (int32_t*)(ws + s.keys_in);
+    int32_t* keys_out = (int32_t*)(ws + s.keys_out);
+    int32_t* vals_in = (int32_t*)(ws + s.vals_in);
+    k_plan_order_keys<<<(unsigned)ceil_div(plan->max_work, 256), 256, 0, stream>>>(*plan, s.top, keys_in, vals_in);
+    size_t tb = s.temp_bytes;
+    HGNN_CHECK_HIP(rocprim::radix_sort_pairs(ws + s.temp, tb, keys_in, keys_out, vals_in, order,
+                                             (size_t)plan->max_work, 0u, (unsigned)key_bits(s.top + 1), stream));
+    HGNN_CHECK_HIP(hipGetLastError());
+    return HGNN_OK;
+}
 
 extern "C" int hgnn_plan_dims(int64_t n_rows, int64_t n_dst, int64_t n_src, int32_t chunk,
                               hgnn_plan* plan) {

@@ -31,6 +31,21 @@ static inline ItemView split_items(const hgnn_plan* p) {
             nullptr, nullptr, nullptr};
 }
 
+// What the fp32 sum kernels take on top of an item list (hgnn_segment_reduce_f32_ex).  `order` != NULL: the wave in
+// slot i takes item order[i].  `arrive` != NULL: a chunk adds to arrive[s] after its partial row is out, and the
+// chunk of split destination s that arrives last sums the rows split_pbegin[s] .. split_pbegin[s + 1] - 1 and
+// writes out[split_dst[s]], so that no combine launch follows.  Both NULL: the two-launch kernels as they were.
+struct ItemExtra {
+    const int32_t* order;
+    int32_t* arrive;
+    const int32_t *split_pbegin, *split_dst, *n_split;
+    int32_t max_split;
+};
+
+static inline ItemExtra item_extra(const hgnn_plan* p, const int32_t* order, int32_t* arrive) {
+    return {order, arrive, p->split_pbegin, p->split_dst, p->counts + HGNN_CNT_SPLIT, (int32_t)p->max_split};
+}
+
 // Row shape of a row of `ncol` 16-byte columns: RL lanes per row (a power of two) and VPL loads per lane, handed
 // to fn as compile-time constants: fn(integral_constant<int, RL>, integral_constant<int, VPL>).  MAX_COLS is the
 // widest row the caller admits (256 columns of 4 floats, 64 columns of 8 bf16).  What else a kernel is

@@ -23,6 +23,8 @@ namespace hgnn {
 
 int g_opt_nt_loads = 1;   // hgnn_set_option("nt_loads"): non-temporal loads for once-read source rows
 int g_opt_nt_stores = 0;  // hgnn_set_option("nt_stores"): non-temporal stores for gather output
+int g_opt_k1_one_launch = 1;  // hgnn_set_option("k1_one_launch"): the chunk that arrives last combines (_f32_ex)
+int g_opt_k1_item_order = 0;  // hgnn_set_option("k1_item_order"): work items longest-first (_f32_ex); not shown to pay
 
 // NT is a template parameter on purpose: written as `nt ? nontemporal_load(p) : *p` with a function argument,
 // both arms load the same address, the helper is optimised before it is inlined, and the two loads are merged
@@ -31,6 +33,36 @@ template <bool NT>
 __device__ __forceinline__ f32x4 ld4(const void* p) {
     if constexpr (NT) return __builtin_nontemporal_load((const f32x4*)p);
     else return *(const f32x4*)p;
+}
+
+// One launch per call (ItemExtra::arrive, rows_common.h): every lane of a wave calls this once its partial row p
+// is stored.  True, wave-uniformly, in the chunk of split destination s that arrives last; it then sums the nch
+// partial rows from pbegin on, in chunk order, into out[dst].  Nobody waits for anybody.
+// The L2s of the eight XCDs are not coherent for plain accesses: the agent-scope release writes this wave's row
+// back (stores drained first, and the write-back waited for by hand, which the compiler has been seen to skip),
+// the acquire of the add drops this CU's stale lines before the rows of the other chunks are read.  The counter
+// goes back to 0 for the next call, which is stream-ordered behind this one: no memset, and a captured graph
+// replays.
+__device__ __forceinline__ bool last_chunk_arrives(const ItemExtra& x, int p, int lane, int& pbegin, int& nch,
+                                                   int& dst) {
+    int s = 0, hi = min(*x.n_split, x.max_split);  // the last s with split_pbegin[s] <= p
+    while (hi - s > 1) {
+        const int mid = (s + hi) >> 1;
+        if (x.split_pbegin[mid] <= p) s = mid;
+        else hi = mid;
+    }
+    pbegin = x.split_pbegin[s];
+    nch = x.split_pbegin[s + 1] - pbegin;
+    dst = x.split_dst[s];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    int seen = 0;
+    if (lane == 0) seen = __hip_atomic_fetch_add(&x.arrive[s], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (__builtin_amdgcn_readfirstlane(seen) != nch - 1) return false;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_store(&x.arrive[s], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return true;
 }
 
 // TAG distinguishes the main pass (0), the partial-sum combine pass (1) and the main pass on a
@@ -42,7 +74,7 @@ __global__ __launch_bounds__(WPB * 64) void k_seg_reduce(
     const float* __restrict__ row_scale, const int32_t* __restrict__ wi_begin,
     const int32_t* __restrict__ wi_end, const int32_t* __restrict__ wi_target,
     const int32_t* __restrict__ n_items_ptr, int64_t max_items, float* __restrict__ out,
-    float* __restrict__ partial) {
+    float* __restrict__ partial, ItemExtra x) {
     constexpr int G = 64 / RL;
     const int lane = threadIdx.x & 63;
     int64_t bid = blockIdx.x;
@@ -52,8 +84,10 @@ __global__ __launch_bounds__(WPB * 64) void k_seg_reduce(
         const int64_t per_xcd = (gridDim.x + 7) / 8;
         bid = (bid % 8) * per_xcd + bid / 8;
     }
-    const int64_t item = bid * WPB + (threadIdx.x >> 6);
+    int64_t item = bid * WPB + (threadIdx.x >> 6);
     const int n_items = *n_items_ptr;
+    if (item >= max_items) return;
+    if (x.order != nullptr) item = x.order[item];  // slots past the count hold items past the count
     if (item >= n_items || item >= max_items) return;
     const int begin = __builtin_amdgcn_readfirstlane(wi_begin[item]);
     const int end = __builtin_amdgcn_readfirstlane(wi_end[item]);
@@ -136,6 +170,42 @@ __global__ __launch_bounds__(WPB * 64) void k_seg_reduce(
             if (cv < nvec) *(f32x4*)(op + cv * 4) = acc[v];
         }
     }
+    if constexpr (!HAS_W && !HAS_RS && TAG != 1) {
+        if (x.arrive != nullptr && target < 0) {
+            int pbegin, nch, dst;
+            if (!last_chunk_arrives(x, ~target, lane, pbegin, nch, dst)) return;
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) acc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+            // the order of the TAG 1 launch, bit for bit: lane group g adds the partial rows g, g + G, .. in
+            // chunk order, then the groups are added as above
+            for (int k = g; k < nch; k += G) {
+                const float* rp = partial + (size_t)(pbegin + k) * (size_t)F;
+#pragma unroll
+                for (int v = 0; v < VPL; ++v) {
+                    const int cv = c + v * 64;
+                    if (cv < nvec) acc[v] += ld4<NT>(rp + cv * 4);
+                }
+            }
+            if (G > 1) {
+#pragma unroll
+                for (int off = RL; off < 64; off <<= 1) {
+#pragma unroll
+                    for (int v = 0; v < VPL; ++v) {
+                        acc[v].x += __shfl_xor(acc[v].x, off);
+                        acc[v].y += __shfl_xor(acc[v].y, off);
+                        acc[v].z += __shfl_xor(acc[v].z, off);
+                        acc[v].w += __shfl_xor(acc[v].w, off);
+                    }
+                }
+            }
+            float* op = out + (size_t)dst * (size_t)F;
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) {
+                const int cv = c + v * 64;
+                if (g == 0 && cv < nvec) *(f32x4*)(op + cv * 4) = acc[v];
+            }
+        }
+    }
 }
 
 // The headline shape (one 1-KiB row per wave instruction, no weight, no row scale): a rolling window of W row
@@ -156,16 +226,19 @@ __global__ __launch_bounds__(WPB * 64) void k_seg_window(
     const float* __restrict__ src, int F, int nvec, const int32_t* __restrict__ src_row,
     const int32_t* __restrict__ wi_begin, const int32_t* __restrict__ wi_end,
     const int32_t* __restrict__ wi_target, const int32_t* __restrict__ n_items_ptr, int64_t max_items,
-    float* __restrict__ out, float* __restrict__ partial) {
+    float* __restrict__ out, float* __restrict__ partial, ItemExtra x) {
     static_assert(W >= 2 && 64 % W == 0, "a 64-row trip is a whole number of windows");
     constexpr bool IDENT = TAG != 0;
     const int lane = threadIdx.x & 63;
-    const int64_t item =
-        (int64_t)blockIdx.x * WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int64_t item = (int64_t)blockIdx.x * WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (item >= max_items) return;
+    // longest lists first (hgnn_plan_item_order): one more scalar load at the head of the chain.  A slot past
+    // the count holds an item past the count; the clamp only keeps a foreign `order` inside the arrays.
+    if (x.order != nullptr) item = x.order[item];
     // four scalar loads issued together: an item past the count (known only now) becomes an empty list that
     // stores nothing, so that none of the loads can be moved behind a branch on the count
     const bool valid = item < *n_items_ptr;
+    item = item < max_items ? item : max_items - 1;
     const int begin = wi_begin[item];
     const int end = begin + (int)(((uint32_t)wi_end[item] - (uint32_t)begin) & (valid ? ~0u : 0u));
     const int target = wi_target[item];
@@ -228,6 +301,26 @@ __global__ __launch_bounds__(WPB * 64) void k_seg_window(
     }
     float* op = target >= 0 ? out + (size_t)target * (size_t)F : partial + (size_t)(~target) * (size_t)F;
     if (valid && lane < nvec) *(f32x4*)(op + lane * 4) = acc;
+    if constexpr (TAG != 1) {
+        if (x.arrive != nullptr && valid && target < 0) {
+            int pbegin, nch, dst;
+            if (!last_chunk_arrives(x, ~target, lane, pbegin, nch, dst)) return;
+            // four partial rows in flight; kept below the eight loads of a window on purpose
+            const char* pp = (const char*)partial + (size_t)pbegin * row_bytes + voff;
+            acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+            for (int k = 0; k < nch; k += 4) {
+                f32x4 part[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) part[u] = ld4<NT>(pp + (size_t)min(k + u, nch - 1) * row_bytes);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (k + u < nch) acc += part[u];
+                }
+            }
+            if (lane < nvec) *(f32x4*)(out + (size_t)dst * (size_t)F + lane * 4) = acc;
+        }
+    }
 }
 
 // any F (including F % 4 != 0): lanes stride over single floats, 64 columns per pass.
@@ -491,6 +584,7 @@ struct SegArgs {
     const float* row_scale;
     float *out, *partial;
     ItemView items;
+    ItemExtra extra;  // zeros: plan order, combine by a second launch
 };
 
 // The one place that decides on non-temporal row loads: fn(bool_constant<NT>).  The partial rows of the combine
@@ -508,7 +602,7 @@ static void launch_seg3(const SegArgs& a, hipStream_t s) {
     const ItemView& v = a.items;
     launch_items<WPB>(k_seg_reduce<RL, VPL, U, W, RS, NT, TAG, WPB, false>, v.max_items, s, a.src, a.F, a.F / 4,
                       v.src_row, v.perm, a.weight, a.row_scale, v.begin, v.end, v.target, v.n_items, v.max_items,
-                      a.out, a.partial);
+                      a.out, a.partial, a.extra);
 }
 
 template <int RL, int VPL, int U, bool W, bool RS, int TAG>
@@ -520,7 +614,7 @@ template <int W, bool NT, int TAG, int WPB>
 static void launch_window(const SegArgs& a, hipStream_t s) {
     const ItemView& v = a.items;
     launch_items<WPB>(k_seg_window<W, NT, TAG, WPB>, v.max_items, s, a.src, a.F, a.F / 4, v.src_row, v.begin, v.end,
-                      v.target, v.n_items, v.max_items, a.out, a.partial);
+                      v.target, v.n_items, v.max_items, a.out, a.partial, a.extra);
 }
 
 #ifdef HGNN_K1_SWEEP
@@ -574,33 +668,55 @@ static void dispatch_seg(const SegArgs& a, hipStream_t s) {
 
 using namespace hgnn;
 
-extern "C" int hgnn_segment_reduce_f32(const hgnn_plan* plan, const float* src, int32_t F,
-                                       const float* weight, const float* row_scale, float* out,
-                                       float* partial, hgnn_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    HGNN_REQUIRE(plan != nullptr, "hgnn_segment_reduce_f32: plan is NULL");
-    HGNN_REQUIRE(F > 0, "hgnn_segment_reduce_f32: F must be positive (got %d)", F);
+// `who` names the entry point in error messages.  arrive == NULL: the combine pass is a second launch.
+static int segment_reduce_f32(const char* who, const hgnn_plan* plan, const float* src, int32_t F,
+                              const float* weight, const float* row_scale, float* out, float* partial,
+                              int32_t* arrive, const int32_t* order, hipStream_t stream) {
+    HGNN_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
+    HGNN_REQUIRE(F > 0, "%s: F must be positive (got %d)", who, F);
     if (plan->n_dst == 0) return HGNN_OK;
-    HGNN_REQUIRE(out != nullptr, "hgnn_segment_reduce_f32: out is NULL");
-    HGNN_REQUIRE(plan->n_rows == 0 || src != nullptr, "hgnn_segment_reduce_f32: src is NULL");
+    HGNN_REQUIRE(out != nullptr, "%s: out is NULL", who);
+    HGNN_REQUIRE(plan->n_rows == 0 || src != nullptr, "%s: src is NULL", who);
     HGNN_REQUIRE(plan->src_row != nullptr || !plan->has_gather,
-                 "hgnn_segment_reduce_f32: src_row may only be NULL for a sorted plan without gather");
-    HGNN_REQUIRE(partial != nullptr || plan->max_partial == 0, "hgnn_segment_reduce_f32: partial is NULL");
+                 "%s: src_row may only be NULL for a sorted plan without gather", who);
+    HGNN_REQUIRE(partial != nullptr || plan->max_partial == 0, "%s: partial is NULL", who);
     HGNN_REQUIRE(((uintptr_t)src % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)partial % 16 == 0) || F % 4 != 0,
-                 "hgnn_segment_reduce_f32: src/out/partial must be 16-byte aligned");
-    const SegArgs a = {src, F, weight, row_scale, out, partial, work_items(plan)};
+                 "%s: src/out/partial must be 16-byte aligned", who);
+    SegArgs a = {src, F, weight, row_scale, out, partial, work_items(plan), ItemExtra{}};
+    // the in-kernel combine and the item order exist in the plain fp32 vector kernels only
+    const bool plain_vec = !weight && !row_scale && F % 4 == 0 && F <= 1024;
+    const bool one_launch = plain_vec && arrive != nullptr && g_opt_k1_one_launch;
+    if (plain_vec) a.extra = item_extra(plan, g_opt_k1_item_order ? order : nullptr, one_launch ? arrive : nullptr);
     if (weight && row_scale) dispatch_seg<true, true, 0>(a, stream);
     else if (weight) dispatch_seg<true, false, 0>(a, stream);
     else if (row_scale) {
-        set_error("hgnn_segment_reduce_f32: row_scale requires weight");
+        set_error("%s: row_scale requires weight", who);
         return HGNN_ERR_UNSUPPORTED;
     } else if (plan->src_row == nullptr) {
         dispatch_seg<false, false, 2>(a, stream);  // TAG 2: sorted-layout (streaming) launches, named apart in profiles
     } else dispatch_seg<false, false, 0>(a, stream);
     // second pass: sum the partial rows of split destinations, in chunk order
-    dispatch_seg<false, false, 1>(SegArgs{partial, F, nullptr, nullptr, out, partial, split_items(plan)}, stream);
+    if (!one_launch)
+        dispatch_seg<false, false, 1>(
+            SegArgs{partial, F, nullptr, nullptr, out, partial, split_items(plan), ItemExtra{}}, stream);
     HGNN_CHECK_HIP(hipGetLastError());
     return HGNN_OK;
+}
+
+extern "C" int hgnn_segment_reduce_f32(const hgnn_plan* plan, const float* src, int32_t F,
+                                       const float* weight, const float* row_scale, float* out,
+                                       float* partial, hgnn_stream_t stream) {
+    return segment_reduce_f32("hgnn_segment_reduce_f32", plan, src, F, weight, row_scale, out, partial, nullptr,
+                              nullptr, (hipStream_t)stream);
+}
+
+extern "C" int hgnn_segment_reduce_f32_ex(const hgnn_plan* plan, const float* src, int32_t F,
+                                          const float* weight, const float* row_scale, float* out,
+                                          float* partial, int32_t* arrive, const int32_t* order,
+                                          hgnn_stream_t stream) {
+    HGNN_REQUIRE(plan == nullptr || arrive != nullptr, "hgnn_segment_reduce_f32_ex: arrive is NULL");
+    return segment_reduce_f32("hgnn_segment_reduce_f32_ex", plan, src, F, weight, row_scale, out, partial, arrive,
+                              order, (hipStream_t)stream);
 }
 
 constexpr int gather_rows_in_flight(int RL, int VPL) { return RL <= 8 ? 2 : RL < 64 ? 4 : VPL == 1 ? 8 : VPL == 2 ? 4 : 2; }

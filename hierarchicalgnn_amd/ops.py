@@ -45,6 +45,15 @@ def _seg_reduce(plan: GraphPlan, src2d: torch.Tensor, weight: Optional[torch.Ten
     lib = _lib.load()
     weight, row_scale = _f32(weight), _f32(row_scale)
     bf16 = src2d.dtype == torch.bfloat16
+    if not bf16 and weight is None and row_scale is None:
+        # plain fp32: one launch per call, work items in the plan's longest-first order where that is switched on
+        order = plan.item_order() if _lib.get_option("k1_item_order") else None
+        with torch.cuda.device(src2d.device):
+            _lib.check(lib.hgnn_segment_reduce_f32_ex(
+                ctypes.byref(plan.c), _lib.ptr(src2d), F, None, None, _lib.ptr(out), _lib.ptr(plan.partial(F)),
+                _lib.ptr(plan.arrive), _lib.ptr(order), _lib.current_stream(src2d.device)),
+                "hgnn_segment_reduce_f32_ex")
+        return out
     fn = lib.hgnn_segment_reduce_bf16 if bf16 else lib.hgnn_segment_reduce_f32
     with torch.cuda.device(src2d.device):
         _lib.check(fn(ctypes.byref(plan.c), _lib.ptr(src2d), F, _lib.ptr(weight), _lib.ptr(row_scale),

@@ -81,6 +81,8 @@ class GraphPlan:
             self.split_dst = _i32(c.max_split, dev)
             self.split_pbegin = _i32(c.max_split + 1, dev)
             self.counts = torch.zeros(8, dtype=torch.int32, device=dev)
+            # arrival counters of hgnn_segment_reduce_f32_ex: zero now, and every call leaves them zero
+            self.arrive = torch.zeros(max(int(c.max_split), 1), dtype=torch.int32, device=dev)
             for name in ("perm", "src_row", "dst32", "rowptr", "wi_begin", "wi_end", "wi_target", "wi_dst",
                          "split_dst", "split_pbegin", "counts"):
                 setattr(c, name, getattr(self, name).data_ptr())
@@ -95,6 +97,7 @@ class GraphPlan:
         self.validated = bool(validate)
         self.sorted = False
         self._partial = {}
+        self._item_order = None
         _STATS["built"] += 1
         if validate:
             # one host sync per plan (= per event), never per aggregation call
@@ -127,6 +130,21 @@ class GraphPlan:
                    torch.empty(n, dtype=torch.int32, device=self.device))
             self._partial[key] = buf
         return buf
+
+    def item_order(self) -> torch.Tensor:
+        """work items longest-first (hgnn_plan_item_order), built on first use: once per plan, never per call"""
+        if self._item_order is None:
+            lib = _lib.load()
+            with torch.inference_mode(False), torch.cuda.device(self.device):
+                order = _i32(self.c.max_work, self.device)
+                nbytes = ctypes.c_size_t(0)
+                _lib.check(lib.hgnn_plan_item_order_workspace_bytes(ctypes.byref(self.c), ctypes.byref(nbytes)),
+                           "hgnn_plan_item_order_workspace_bytes")
+                ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=self.device)
+                _lib.check(lib.hgnn_plan_item_order(ctypes.byref(self.c), _lib.ptr(order), _lib.ptr(ws), ws.numel(),
+                                                    _lib.current_stream(self.device)), "hgnn_plan_item_order")
+            self._item_order = order
+        return self._item_order
 
     def counts_host(self):
         c = self.counts.cpu().tolist()

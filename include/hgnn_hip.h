@@ -51,7 +51,8 @@ extern "C" {
 #define HGNN_ERR_UNSUPPORTED 4
 
 /* hgnn_assign_match and hgnn_assign_match_workspace_bytes were added without a bump: they are additions, and
- * no existing entry point, struct or constant changed layout or meaning. */
+ * no existing entry point, struct or constant changed layout or meaning.  The same holds for
+ * hgnn_segment_reduce_f32_ex, hgnn_plan_item_order(_workspace_bytes) and hgnn_get_option. */
 #define HGNN_ABI_VERSION 26
 
 typedef void* hgnn_stream_t; /* hipStream_t */
@@ -122,8 +123,15 @@ int hgnn_sizeof_mlp_desc(void);
  *                  refused unless the environment variable HGNN_EXPERIMENTAL is set
  *   "mlp_split3_one_wg"  DIAGNOSTIC: 1 launches one persistent workgroup per CU where two fit (results must be
  *                  bitwise the same: tests/test_gpu_split3.py)
+ *   "k1_one_launch" 1 (default): in hgnn_segment_reduce_f32_ex the chunk of a split destination that arrives last
+ *                  sums its partial rows, and no combine launch follows; 0 the two launches of hgnn_segment_reduce_f32
+ *   "k1_item_order" 0 (default): plan order; 1: hgnn_segment_reduce_f32_ex hands the work items out in the order
+ *                  it is given (hgnn_plan_item_order: longest lists first).  Off until a measurement shows that it
+ *                  pays.  Results do not depend on either option.
  * Any other name is an error (HGNN_ERR_INVALID_ARG). */
 int hgnn_set_option(const char* name, int value);
+/* the current value of an option */
+int hgnn_get_option(const char* name, int* value);
 
 /* Fills n_rows/n_dst/n_src/chunk/max_* of `plan` (pointers untouched).
  * chunk <= 0 selects the default rule (quarter of a wave's share of the rows,
@@ -146,6 +154,27 @@ int hgnn_plan_build(const int64_t* dst_index, const int64_t* gather_index, hgnn_
 int hgnn_segment_reduce_f32(const hgnn_plan* plan, const float* src, int32_t F,
                             const float* weight, const float* row_scale,
                             float* out, float* partial, hgnn_stream_t stream);
+
+/* The same sums, bit for bit, with two device arrays that are not part of hgnn_plan:
+ *   arrive  int32[max(plan->max_split, 1)], all zero when first handed in and left all zero by every call.  Plain
+ *           fp32 rows of 4-element columns (no weight, F % 4 == 0, F <= 1024) then need ONE launch: each chunk of
+ *           a split destination adds to arrive[split] once its partial row is out, and the chunk that arrives last
+ *           sums the partial rows, in chunk order, into the output row.  No wave waits for another.  Every other
+ *           form runs the two launches of hgnn_segment_reduce_f32.
+ *   order   int32[plan->max_work] from hgnn_plan_item_order, or NULL for plan order (same forms as above).
+ * `partial` and `arrive` belong to one call at a time: two calls on one plan that may overlap (different streams)
+ * need buffers of their own, as they always did for `partial`. */
+int hgnn_segment_reduce_f32_ex(const hgnn_plan* plan, const float* src, int32_t F,
+                               const float* weight, const float* row_scale, float* out, float* partial,
+                               int32_t* arrive, const int32_t* order, hgnn_stream_t stream);
+
+/* order[0 .. max_work): the work items of a built plan by non-increasing list length in buckets of 8 rows,
+ * plan order kept inside a bucket; entries past counts[HGNN_CNT_WORK] hold indices >= that count.  Long lists
+ * that start late keep a launch open while most of the chip is idle; this starts them first.  Built once per plan.
+ * workspace: device scratch of hgnn_plan_item_order_workspace_bytes (needs the plan's dims only). */
+int hgnn_plan_item_order_workspace_bytes(const hgnn_plan* plan, size_t* bytes);
+int hgnn_plan_item_order(const hgnn_plan* plan, int32_t* order, void* workspace, size_t workspace_bytes,
+                         hgnn_stream_t stream);
 
 /* Segmented min / max with arg output, and exact integer sums, over a plain destination plan (no gather index):
  * torch_scatter.scatter_min / scatter_max (BipartiteClassification/bipartite_classification_base.py:158,
