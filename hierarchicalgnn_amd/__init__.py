@@ -10,6 +10,7 @@ Drop-in surface (same names / signatures as the reference):
     graph_intersection(...), frnn_graph(...)             <- Modules/utils.py (embedding stage)
     bipartite_loss(...), bc_training_loss(...)           <- BipartiteClassificationBase.get_bipartite_loss / training_step
     pair_hinge_loss(...), embedding_hgnn_training_loss(...)   <- EmbeddingBase.training_step's weighted hinge loss
+    weighted_bce_loss(...), ec_training_loss(...), ec_shared_evaluation(...)   <- EdgeClassifierBase.training_step / shared_evaluation
     hdbscan(points, min_cluster_size), embedding_track_candidates(...)   <- cuml.cluster.HDBSCAN (embedding validation)
 
 Everything on the hot path runs in hand-written HIP kernels loaded from
@@ -30,5 +31,7 @@ from .embedding import (pair_hinge_loss, pair_hinge_check, embedding_hgnn_traini
                         embedding_in_training_loss)
 from .assignment import (max_weight_matching, bipartite_loss, bc_embedding_loss, bc_training_loss,  # noqa: F401
                          gap_bound)
+from .edge_classifier import (weighted_bce_loss, weighted_bce_check, ec_training_loss,  # noqa: F401
+                              ec_shared_evaluation)
 
 __version__ = "0.1.0"

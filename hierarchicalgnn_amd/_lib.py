@@ -42,6 +42,11 @@ PH_MAX_DIM = 16
 PH_HPARAMS = 8
 PH_KT, PH_KF, PH_ST, PH_SF, PH_LOSS = range(5)
 PH_STATE = 8
+# HGNN_WB_*: hgnn_weighted_bce_*'s combine modes, status bits and device state vector (hparams: PH_* entries 0-4)
+WB_COMBINE_SUM, WB_COMBINE_MAX = 0, 1
+WB_ST_BAD_ID, WB_ST_BAD_SCORE = 1, 2
+WB_KT, WB_KF, WB_ST, WB_SF, WB_LOSS = range(5)
+WB_STATE = 8
 
 class HgnnPlan(Structure):
     """mirror of ``struct hgnn_plan``"""
@@ -161,6 +166,13 @@ _SIGNATURES = {
     "hgnn_pair_hinge_backward": (c_int, [POINTER(HgnnPlan), c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p,
                                          c_void_p, c_int64, POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_size_t, c_void_p]),
+    "hgnn_weighted_bce_workspace_bytes": (c_int, [c_int64, c_int32, POINTER(c_size_t)]),
+    "hgnn_weighted_bce_forward": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                          c_int64, c_int64, c_int32, POINTER(c_double), c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_size_t, c_void_p]),
+    "hgnn_weighted_bce_backward": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                           c_int64, c_int64, c_int32, POINTER(c_double), c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
 }
 
 _lib = None

@@ -120,26 +120,13 @@ def _asgmt_weight(batch_pt, pt, bipartite_graph, n_cols, y_idx, not_y_idx, row_m
     return weights.float()
 
 
-def bipartite_loss(bipartite_scores, bipartite_graph, batch, hparams, return_details: bool = False):
-    """BipartiteClassificationBase.get_bipartite_loss / gMRTBase.get_bipartite_loss: the pT-weighted BCE between the
-    scores and the truth a maximum-weight particle <-> cluster matching induces.  ``batch``: anything with ``pid``
-    and ``pt`` (attributes or keys) on the scores' device; ``hparams``: weight_leak, ptcut, pt_interval, weight_min,
-    log_weight_ratio.  The gradient reaches ``bipartite_scores`` through the BCE only.  With ``return_details`` also
-    a dict of row_match, col_match (after the noise / virtual filter), truth and weights."""
-    if not torch.is_tensor(bipartite_scores) or not bipartite_scores.is_cuda or not bipartite_graph.is_cuda:
-        raise RuntimeError("bipartite_loss needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
-    if bipartite_graph.shape[1] == 0:
-        raise ValueError("bipartite_loss: empty bipartite graph")
+def _torch_tail(bipartite_scores, bipartite_graph, batch_pt, pt, original_pid, hit_row, col_match, n_cols, hparams,
+                return_details):
+    """everything of get_bipartite_loss after the matching as the reference writes it (:170-190): four ``nonzero()``
+    host reads, get_asgmt_weight, binary_cross_entropy and the dot product"""
     dev = bipartite_scores.device
-    batch_pid, batch_pt = _field(batch, "pid"), _field(batch, "pt")
-    original_pid, pid, _ = torch.unique(batch_pid, return_inverse=True, return_counts=True)   # host read 1
     n_rows = int(original_pid.numel())
-    pt = scatter_min(batch_pt, pid, dim=0, dim_size=n_rows)[0]
     with torch.no_grad():
-        n_cols = int(bipartite_graph[1].max()) + 1                                            # host read 2
-        hit_row = pid[bipartite_graph[0]]
-        col_match = max_weight_matching(hit_row, bipartite_graph[1], bipartite_scores, n_rows, n_cols)[0]
-        reads = stats["host_reads"] + 2
         row_match = torch.arange(n_rows, device=dev)
         noise_mask = (original_pid[row_match] != 0) & (col_match < n_cols)   # filter out noise and virtual tracks
         keep = noise_mask.nonzero().reshape(-1)                                               # read
@@ -153,13 +140,75 @@ def bipartite_loss(bipartite_scores, bipartite_graph, batch, hparams, return_det
         truth = torch.zeros(len(bipartite_scores), dtype=torch.bool, device=dev)
         truth[matched_hits] = pid_assignments[hit_row[matched_hits]] == bipartite_graph[1][matched_hits]
         y_idx, not_y_idx = truth.nonzero().reshape(-1), (~truth).nonzero().reshape(-1)        # two reads
-        stats["host_reads"] = reads + 4
+        stats["host_reads"] += 4
     weights = _asgmt_weight(batch_pt, pt, bipartite_graph, n_cols, y_idx, not_y_idx, row_match, col_match, hparams)
     asgmt_loss = torch.nn.functional.binary_cross_entropy(bipartite_scores, truth.float(), reduction="none")
     asgmt_loss = torch.dot(asgmt_loss, weights)   # weight by pT
     if return_details:
         return asgmt_loss, {"row_match": row_match, "col_match": col_match, "truth": truth, "weights": weights}
     return asgmt_loss
+
+
+def _fused_tail(bipartite_scores, bipartite_graph, batch_pt, pt, original_pid, hit_row, col_match, n_cols, hparams,
+                return_details):
+    """everything of get_bipartite_loss after the matching without a host read: the truth and the supernodes' pt as
+    elementwise index ops over the UNFILTERED matching, the loss as one ``weighted_bce_loss`` call (csrc/wbce.hip)"""
+    from .edge_classifier import _wb_apply
+    dev = bipartite_scores.device
+    n_rows = int(original_pid.numel())
+    with torch.no_grad():
+        matched = (original_pid != 0) & (col_match < n_cols)            # filter out noise and virtual tracks
+        cm = col_match[hit_row]
+        truth = matched[hit_row] & (cm == bipartite_graph[1])
+        # one scatter: a matched particle writes its pt to its column, every other one to its own virtual column
+        # (col_match has no column twice, virtual ones included), and the virtual columns are sliced away
+        slot = torch.where(matched, col_match, n_cols + torch.arange(n_rows, device=dev))
+        supernodes_pt = torch.zeros(n_cols + n_rows, dtype=torch.float32, device=dev)
+        supernodes_pt[slot] = pt.float()
+        supernodes_pt = supernodes_pt[:n_cols]
+    scores = bipartite_scores if bipartite_scores.dtype == torch.float32 else bipartite_scores.float()
+    asgmt_loss, _, state = _wb_apply(scores.reshape(-1), bipartite_graph, truth, batch_pt.float(), hparams,
+                                     supernodes_pt, "max", None)
+    if not return_details:
+        return asgmt_loss
+    with torch.no_grad():
+        keep = matched.nonzero().reshape(-1)                                                  # read
+        stats["host_reads"] += 1
+        raw = torch.maximum(pt_weighting(batch_pt[bipartite_graph[0]], hparams),
+                            pt_weighting(supernodes_pt[bipartite_graph[1]], hparams))
+        k = torch.where(truth, state[_lib.WB_KT], state[_lib.WB_KF])
+        weights = (raw.double() * k).float()
+    return asgmt_loss, {"row_match": keep, "col_match": col_match[keep], "truth": truth, "weights": weights}
+
+
+def bipartite_loss(bipartite_scores, bipartite_graph, batch, hparams, return_details: bool = False,
+                   fused: bool = False):
+    """BipartiteClassificationBase.get_bipartite_loss / gMRTBase.get_bipartite_loss: the pT-weighted BCE between the
+    scores and the truth a maximum-weight particle <-> cluster matching induces.  ``batch``: anything with ``pid``
+    and ``pt`` (attributes or keys) on the scores' device; ``hparams``: weight_leak, ptcut, pt_interval, weight_min,
+    log_weight_ratio.  The gradient reaches ``bipartite_scores`` through the BCE only.  With ``return_details`` also
+    a dict of row_match, col_match (after the noise / virtual filter), truth and weights.  ``fused=True`` evaluates
+    everything after ``max_weight_matching`` with no host read (four fewer than the default route): truth and the
+    supernodes' pt by index ops, the weights, the BCE and the dot product as ``edge_classifier.weighted_bce_loss``
+    (``combine="max"``); the weights are materialised only for ``return_details``, whose filter is then one read."""
+    if not torch.is_tensor(bipartite_scores) or not bipartite_scores.is_cuda or not bipartite_graph.is_cuda:
+        raise RuntimeError("bipartite_loss needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
+    if bipartite_graph.shape[1] == 0:
+        raise ValueError("bipartite_loss: empty bipartite graph")
+    batch_pid, batch_pt = _field(batch, "pid"), _field(batch, "pt")
+    original_pid, pid, _ = torch.unique(batch_pid, return_inverse=True, return_counts=True)   # host read 1
+    n_rows = int(original_pid.numel())
+    pt = scatter_min(batch_pt, pid, dim=0, dim_size=n_rows)[0]
+    with torch.no_grad():
+        n_cols = int(bipartite_graph[1].max()) + 1                                            # host read 2
+        hit_row = pid[bipartite_graph[0]]
+        col_match = max_weight_matching(hit_row, bipartite_graph[1], bipartite_scores, n_rows, n_cols)[0]
+        stats["host_reads"] += 2
+    if fused:
+        return _fused_tail(bipartite_scores, bipartite_graph, batch_pt, pt, original_pid, hit_row, col_match, n_cols,
+                           hparams, return_details)
+    return _torch_tail(bipartite_scores, bipartite_graph, batch_pt, pt, original_pid, hit_row, col_match, n_cols,
+                       hparams, return_details)
 
 
 def bc_embedding_loss(embeddings, edge_index, batch, hparams, fused=False):
@@ -181,10 +230,11 @@ def bc_embedding_loss(embeddings, edge_index, batch, hparams, fused=False):
     return torch.dot(emb_loss, weights)
 
 
-def bc_training_loss(bipartite_graph, bipartite_scores, embeddings, batch, hparams, loss_schedule):
+def bc_training_loss(bipartite_graph, bipartite_scores, embeddings, batch, hparams, loss_schedule, fused=False):
     """training_step (:196-213) after the forward: (loss, emb_loss, asgmt_loss) with
-    loss = loss_schedule * emb_loss + (1 - loss_schedule) * asgmt_loss.  ``batch`` also carries ``edge_index``."""
-    emb_loss = bc_embedding_loss(embeddings, _field(batch, "edge_index"), batch, hparams)
-    asgmt_loss = bipartite_loss(bipartite_scores, bipartite_graph, batch, hparams)
+    loss = loss_schedule * emb_loss + (1 - loss_schedule) * asgmt_loss.  ``batch`` also carries ``edge_index``.
+    ``fused=True`` takes the fused route of both terms (``bc_embedding_loss``, ``bipartite_loss``)."""
+    emb_loss = bc_embedding_loss(embeddings, _field(batch, "edge_index"), batch, hparams, fused=fused)
+    asgmt_loss = bipartite_loss(bipartite_scores, bipartite_graph, batch, hparams, fused=fused)
     loss = (loss_schedule * emb_loss) + ((1 - loss_schedule) * asgmt_loss)
     return loss, emb_loss, asgmt_loss

@@ -28,13 +28,13 @@ struct PhParams {
     float margin, scale;
 };
 
-__device__ __forceinline__ float ph_ptw(float p, const PhParams& q) {
-    if (p != p) p = 0.f;                                     // embedding_base.py:97
-    const float x = p - q.cut, z = p - q.cap;
-    float r = (x > 0.f ? 1.f : 0.f) * x / q.interval;        // heaviside(x, 0) * x / (cap - cut)
-    r = (r != r) ? r : fminf(r, 1.f);                        // torch.minimum keeps NaN (interval == 0)
-    return q.wmin + q.one_minus_wmin * r + q.leak * (z > 0.f ? 1.f : 0.f) * z;
-}
+}  // namespace
+}  // namespace hgnn
+// ph_ptw(pt, params): pt_weighting in float32 with a NaN pt read as 0.  It lives in a header of its own because
+// k_wb_* (wbce.hip, the weighted BCE) weighs the endpoints of its pairs with the same function.
+#include "ptw.h"
+namespace hgnn {
+namespace {
 
 template <bool V4>
 __device__ __forceinline__ float ph_dist(const float* __restrict__ E, int64_t a, int64_t b, int D) {

@@ -679,6 +679,51 @@ int hgnn_pair_hinge_backward(const hgnn_plan* plan, const float* E, int64_t N, i
                              const double* state, const float* grad_out, float* grad_E, void* workspace,
                              size_t workspace_bytes, hgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * pT-weighted binary cross-entropy: the edge classifier's loss (reference EdgeClassifier/edge_classifier_base.py
+ * :99-111, :127-128) and the assignment loss after the matching (bipartite_classification_base.py:123-138, :189-190)
+ * as one operator.  Added under ABI 26: additions only.
+ *
+ * scores float32 [P] in [0, 1]; graph [2, P] pair ids (row a in [0, NA), then row b in [0, NB); int32 or int64 by
+ * index_dtype); y uint8 [P] (!= 0 = true pair); keep uint8 [P] or NULL (NULL = every pair; a pair with keep == 0
+ * contributes to nothing); pt_a float32 [NA], pt_b float32 [NB] (the same pointer for one table); combine =
+ * HGNN_WB_COMBINE_SUM (edge classifier) or HGNN_WB_COMBINE_MAX (assignment); hparams: HOST double[HGNN_PH_HPARAMS],
+ * entries HGNN_PH_WEIGHT_MIN .. HGNN_PH_LOG_WEIGHT_RATIO (0-4) are read, before the call returns.  Definition
+ * ("k_wb"), ptw as for the pair hinge:
+ *     raw_i = combine(ptw(pt_a[a_i]), ptw(pt_b[b_i])),  S_T = sum_{keep, y} raw_i,  S_F = sum_{keep, !y} raw_i
+ *     l_i = -(y_i ? max(log(s_i), -100) : max(log(1 - s_i), -100))   (float32, 1 - s_i formed in float32)
+ *     loss = sigmoid(lwr) / S_T * sum_{keep, y} raw_i l_i + sigmoid(-lwr) / S_F * sum_{keep, !y} raw_i l_i
+ *   A class whose weights sum to 0 contributes nothing (the reference's 0/0 is NaN); P = 0 gives 0.  The four sums
+ *   are float64 sums in a fixed order that depends on P alone: two calls give the same bits.
+ * hgnn_weighted_bce_forward: loss device float[1]; state device double[HGNN_WB_STATE] (indices below); status device
+ *   int32[1], cleared first, then the OR of HGNN_WB_ST_BAD_ID (an id out of range) and HGNN_WB_ST_BAD_SCORE (a score
+ *   that is NaN or outside [0, 1]); such pairs are skipped like dropped ones, never a fault.
+ * hgnn_weighted_bce_backward: grad_scores float32 [P], every element written:
+ *     grad_out[0] * k_class(i) * raw_i * (s_i - y_i) / max((1 - s_i) * s_i, 1e-12),  0 for a dropped or skipped pair;
+ *   grad_out device float[1]; state as the forward wrote it.  No atomics, no workspace.
+ * Both launch asynchronously, allocate nothing and never synchronise.
+ * hgnn_weighted_bce_workspace_bytes: device scratch of one forward (backward = 0) or backward (1) call.
+ * ------------------------------------------------------------------------ */
+#define HGNN_WB_COMBINE_SUM 0
+#define HGNN_WB_COMBINE_MAX 1
+#define HGNN_WB_ST_BAD_ID 1
+#define HGNN_WB_ST_BAD_SCORE 2
+#define HGNN_WB_KT 0     /* sigmoid(lwr) / S_T, 0 for a class without weight */
+#define HGNN_WB_KF 1     /* sigmoid(-lwr) / S_F                               */
+#define HGNN_WB_ST 2
+#define HGNN_WB_SF 3
+#define HGNN_WB_LOSS 4   /* the loss before it is rounded to float32          */
+#define HGNN_WB_STATE 8
+int hgnn_weighted_bce_workspace_bytes(int64_t P, int32_t backward, size_t* bytes);
+int hgnn_weighted_bce_forward(const float* scores, const void* graph, int32_t index_dtype, const uint8_t* y,
+                              const uint8_t* keep, const float* pt_a, int64_t NA, const float* pt_b, int64_t NB,
+                              int64_t P, int32_t combine, const double* hparams, float* loss, double* state,
+                              int32_t* status, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
+int hgnn_weighted_bce_backward(const float* scores, const void* graph, int32_t index_dtype, const uint8_t* y,
+                               const uint8_t* keep, const float* pt_a, int64_t NA, const float* pt_b, int64_t NB,
+                               int64_t P, int32_t combine, const double* hparams, const double* state,
+                               const float* grad_out, float* grad_scores, hgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
