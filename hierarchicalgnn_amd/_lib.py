@@ -114,6 +114,9 @@ _SIGNATURES = {
     "hgnn_knn_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, POINTER(c_size_t)]),
     "hgnn_knn_radius_ws_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_float, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hgnn_knn_sorted_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, c_int32, POINTER(c_size_t)]),
+    "hgnn_knn_radius_sorted_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_float, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "hgnn_gmm2_fit_f32": (c_int, [c_void_p, c_int64, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                   c_void_p]),
     "hgnn_gmm2_cut_f32": (c_int, [c_void_p, c_float, c_int32, c_float, c_void_p, c_void_p]),

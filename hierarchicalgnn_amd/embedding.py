@@ -4,8 +4,9 @@ Every training step of Embedding-IN / Embedding-HGNN-GMM calls ``get_training_sa
 fixed-radius kNN graph of the embeddings with knn = 100 (frnn, CUDA-only, there) and ``graph_intersection``
 (utils.py:117-166, scipy CSR on the host there).  Here:
 
-    frnn_graph(embeddings, r, k)                     utils.FRNN_graph: ops.knn_radius (k <= 128, csrc/knn_large.hip
-                                                     for k > 32), [2, E] int64, query ascending, then slot order
+    frnn_graph(embeddings, r, k, method=None)        utils.FRNN_graph: ops.knn_radius (k <= 128, csrc/knn_large.hip
+                                                     for k > 32, csrc/knn_sorted.hip with method="sorted"), [2, E]
+                                                     int64, query ascending, then slot order
     graph_intersection(pred_graph, truth_graph, using_weights=False, weights_bidir=None)
                                                      utils.graph_intersection: one hgnn_graph_intersection call
                                                      (csrc/intersect.hip) and ONE host read (the count and status)
@@ -41,13 +42,18 @@ def _field(batch, name):
     return batch[name] if isinstance(batch, dict) else getattr(batch, name)
 
 
-def frnn_graph(embeddings: torch.Tensor, r, k: int) -> torch.Tensor:
+# DESIGN.md section 3 "k_knn_sorted" records the measurement this default rests on
+FRNN_DEFAULT_METHOD = "brute"
+
+
+def frnn_graph(embeddings: torch.Tensor, r, k: int, method=None) -> torch.Tensor:
     """utils.FRNN_graph (utils.py:241-252): the pairs (query, neighbour) of the fixed-radius kNN of the embeddings
     among themselves, self pairs included, int64 [2, E] with the query ascending and then the neighbours in slot order
-    (ascending distance, ties to the lower index)."""
+    (ascending distance, ties to the lower index).  ``method``: ops.knn_radius's ("brute" or "sorted": the same
+    graph bit for bit); None = the default, FRNN_DEFAULT_METHOD."""
     if not embeddings.is_cuda:
         raise RuntimeError("frnn_graph needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
-    idx = knn_radius(embeddings, embeddings, int(k), r)
+    idx = knn_radius(embeddings, embeddings, int(k), r, method=FRNN_DEFAULT_METHOD if method is None else method)
     pos = idx >= 0
     ind = torch.arange(idx.shape[0], device=idx.device).unsqueeze(1).expand(idx.shape)
     return torch.stack([ind[pos], idx[pos]], dim=0)
@@ -110,13 +116,19 @@ def graph_intersection(pred_graph, truth_graph, using_weights=False, weights_bid
     return new_graph, y
 
 
+def _knn_method(hparams):
+    """the optional hparams["knn_method"] (None: the default)"""
+    return hparams["knn_method"] if "knn_method" in hparams else None
+
+
 def training_samples(embeddings, batch, hparams, prediction_graph=None):
     """EmbeddingBase.get_training_samples (embedding_base.py:109-135) for both ``true_edges`` modes.  ``batch``:
     anything with ``modulewise_true_edges``, ``signal_mask`` and ``pid`` (attributes or keys) on the embeddings'
-    device.  ``prediction_graph`` replaces the kNN graph when given (the reference always builds it)."""
+    device.  ``prediction_graph`` replaces the kNN graph when given (the reference always builds it); the optional
+    ``hparams["knn_method"]`` is frnn_graph's ``method``."""
     dev = embeddings.device
     if prediction_graph is None:
-        prediction_graph = frnn_graph(embeddings, hparams["train_r"], hparams["knn"])
+        prediction_graph = frnn_graph(embeddings, hparams["train_r"], hparams["knn"], _knn_method(hparams))
     mte = _field(batch, "modulewise_true_edges")
     signal_mask = _field(batch, "signal_mask")
     pid = _field(batch, "pid")

@@ -5,7 +5,8 @@ attention weights of the hierarchical model.
 Same constructor (``weighting_function`` name, ``hparams``), buffers (``knn_radius``) and
 sub-module (``weight_normalization`` = ``BatchNorm1d(1)``), hence the same ``state_dict``
 keys.  The neighbour search runs in the exact brute-force HIP kernel
-(``hgnn_knn_radius_f32``) instead of the un-vendored ``frnn`` grid search; the per-edge
+(``hgnn_knn_radius_f32``; with ``hparams["knn_method"] = "sorted"`` in the spatially sorted
+``hgnn_knn_radius_sorted_f32``, same result) instead of the un-vendored ``frnn`` grid search; the per-edge
 dot products use ``hgnn_edge_dot_f32`` (no gathered copies), differentiable w.r.t. both
 embeddings.  ``symmetrize`` restates cugraph's (union of both directions, duplicates
 removed); cugraph does not document an edge order, ours is sorted by (src, dst).
@@ -18,11 +19,13 @@ import torch.nn as nn
 from .ops import edge_dot, knn_radius
 
 
-def find_neighbors(embedding1, embedding2, r_max=1.0, k_max=10, return_dist2=False):
+def find_neighbors(embedding1, embedding2, r_max=1.0, k_max=10, return_dist2=False, method=None):
+    # method: ops.knn_radius's; None = "brute" (k_max in 1-6, 8, 10, 12, 16, 20, 32 or 33..128); "sorted": every k_max
     # a tensor radius (the knn_radius buffer) is read by the kernel itself: no .item() host read
     r = r_max if torch.is_tensor(r_max) and r_max.is_cuda else (float(r_max.item()) if torch.is_tensor(r_max)
                                                                  else float(r_max))
-    return knn_radius(embedding1, embedding2, k_max, r, return_dist2=return_dist2)
+    return knn_radius(embedding1, embedding2, k_max, r, return_dist2=return_dist2,
+                      method="brute" if method is None else method)
 
 
 def symmetrize(src: torch.Tensor, dst: torch.Tensor, n: int):
@@ -64,13 +67,15 @@ class DynamicGraphConstruction(nn.Module):
         self.weight_normalization = nn.BatchNorm1d(1)
         self.weighting_function = getattr(torch, weighting_function)
         self.register_buffer("knn_radius", torch.ones(1), persistent=True)
+        # optional hparams["knn_method"]: "sorted" takes every k (a sparsity sweep at k = 7 or 9); absent: "brute"
+        self.knn_method = hparams["knn_method"] if hparams is not None and "knn_method" in hparams else None
 
     def build_graph(self, src_embeddings, dst_embeddings, sym=False, k=10):
         """gnn_utils.py:193-205 (no gradients): kNN within the tracked radius, optional symmetrisation,
         radius EMA in training mode"""
         with torch.no_grad():
             idxs, d2 = find_neighbors(src_embeddings, dst_embeddings, r_max=self.knn_radius, k_max=k,
-                                      return_dist2=True)
+                                      return_dist2=True, method=self.knn_method)
             positive = idxs >= 0
             ind = torch.arange(idxs.shape[0], device=idxs.device).unsqueeze(1).expand(idxs.shape)
             if sym:

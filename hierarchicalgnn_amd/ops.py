@@ -503,11 +503,21 @@ def edge_dot(A: torch.Tensor, ai: torch.Tensor, B: torch.Tensor, bi: torch.Tenso
     return _EdgeDot.apply(A, B, ai, bi)
 
 
-def knn_radius(query: torch.Tensor, points: torch.Tensor, k: int, radius, return_dist2: bool = False):
+KNN_METHODS = ("brute", "sorted")
+_knn_sorted_stats = None   # device int64[2] of the last method="sorted" call
+
+
+def knn_radius(query: torch.Tensor, points: torch.Tensor, k: int, radius, return_dist2: bool = False,
+               method: str = "brute"):
     """<=k nearest `points` of every `query` row with squared distance < radius^2, ascending,
     -1 padded: the idxs of frnn.frnn_grid_points (Modules/utils.py:232) for one batch.
     ``radius``: a float, or a 1-element float32 device tensor (the module's ``knn_radius`` buffer) that the
-    kernel reads itself -- no host read of it."""
+    kernel reads itself -- no host read of it.
+    ``method``: "brute" compares every query with every point (k in 1-6, 8, 10, 12, 16, 20, 32 or 33..128);
+    "sorted" sorts the points along a Morton curve and skips tiles that are provably too far (csrc/knn_sorted.hip):
+    the same result bit for bit, for every k in 1..128."""
+    if method not in KNN_METHODS:
+        raise ValueError(f"knn_radius: method must be one of {KNN_METHODS}, got {method!r}")
     _require_hip(query, "query")
     _require_hip(points, "points")
     if query.dim() != 2 or points.dim() != 2 or query.shape[1] != points.shape[1]:
@@ -525,6 +535,20 @@ def knn_radius(query: torch.Tensor, points: torch.Tensor, k: int, radius, return
     d2 = torch.empty((nq, int(k)), dtype=torch.float32, device=q.device) if return_dist2 else None
     lib = _lib.load()
     nbytes = ctypes.c_size_t(0)
+    if method == "sorted":
+        global _knn_sorted_stats
+        _lib.check(lib.hgnn_knn_sorted_workspace_bytes(nq, int(p.shape[0]), D, int(k), ctypes.byref(nbytes)),
+                   "hgnn_knn_sorted_workspace_bytes")
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=q.device)
+        stats = (torch.empty if nq else torch.zeros)(2, dtype=torch.int64, device=q.device)   # nq == 0: not written
+        with torch.cuda.device(q.device):
+            _lib.check(lib.hgnn_knn_radius_sorted_f32(_lib.ptr(q), nq, _lib.ptr(p), int(p.shape[0]), D, int(k),
+                                                      ctypes.c_float(r_val), _lib.ptr(r_dev), _lib.ptr(idx),
+                                                      _lib.ptr(d2), _lib.ptr(ws), nbytes.value, _lib.ptr(stats),
+                                                      _lib.current_stream(q.device)),
+                       "hgnn_knn_radius_sorted_f32")
+        _knn_sorted_stats = stats
+        return (idx, d2) if return_dist2 else idx
     _lib.check(lib.hgnn_knn_workspace_bytes(nq, int(p.shape[0]), int(k), ctypes.byref(nbytes)),
                "hgnn_knn_workspace_bytes")
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=q.device) if nbytes.value else None
@@ -534,6 +558,15 @@ def knn_radius(query: torch.Tensor, points: torch.Tensor, k: int, radius, return
                                               _lib.ptr(ws), nbytes.value, _lib.current_stream(q.device)),
                    "hgnn_knn_radius_ws_f32")
     return (idx, d2) if return_dist2 else idx
+
+
+def knn_radius_stats():
+    """(tiles visited, tiles skipped), summed over the workgroups, of the last ``knn_radius(..., method="sorted")``
+    call.  One host read: for tests and tools, not for a training step."""
+    if _knn_sorted_stats is None:
+        raise RuntimeError("knn_radius_stats: no knn_radius(..., method=\"sorted\") call yet")
+    v, s = _knn_sorted_stats.tolist()
+    return int(v), int(s)
 
 
 def wgrad_bf16(dz: torch.Tensor, rows: torch.Tensor, out: Optional[torch.Tensor] = None,

@@ -266,6 +266,21 @@ int hgnn_knn_radius_ws_f32(const float* query, int64_t nq, const float* points, 
                            int32_t K, float radius, const float* radius_dev, int64_t* idx_out, float* dist2_out,
                            void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
 
+/* The same search -- the K smallest (d2, idx) pairs with d2 < radius^2, bit for bit what the two entries above
+ * return -- without comparing every query with every point (csrc/knn_sorted.hip): the points are sorted along a
+ * Morton curve and cut into tiles of 256 with a box each, 16 curve-consecutive queries visit the tiles from their
+ * home tile outwards and skip a tile whose box is provably too far ("k_knn_sorted").  EVERY K in
+ * [1, 128], D in [1, 16], nq != np allowed; query == points with nq == np shares one sort.  All stages run on
+ * `stream` from `workspace` (hgnn_knn_sorted_workspace_bytes; 16-byte aligned; required): no host read, no
+ * allocation.  After the call the int64[2] at workspace offset 0 holds {tiles visited, tiles skipped} summed over
+ * the workgroups (visited + skipped = workgroups x tiles); `stats_out` (device int64[2], may be NULL) receives a
+ * copy.  nq == 0 returns HGNN_OK; np == 0 fills the outputs with -1. */
+int hgnn_knn_sorted_workspace_bytes(int64_t nq, int64_t np, int32_t D, int32_t K, size_t* bytes);
+int hgnn_knn_radius_sorted_f32(const float* query, int64_t nq, const float* points, int64_t np, int32_t D,
+                               int32_t K, float radius, const float* radius_dev, int64_t* idx_out,
+                               float* dist2_out, void* workspace, size_t workspace_bytes,
+                               int64_t* stats_out, hgnn_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * The hierarchy decision of HierarchicalGNNBlock.clustering
  * (BipartiteClassification/Models/HGNN_GMM.py:162-234) without host round trips.
