@@ -15,7 +15,8 @@
 // (gemm_lds); the epilogue works in the accumulator layout (lane = row, registers = features):
 //   * z' is loaded in that layout as raw bf16 (2 registers per 4 values) and converted each time it is needed,
 //     so that da (128 registers) and z' (64) fit beside each other;
-//   * row statistics / the two LayerNorm-backward row sums cross the 4 waves through LDS, as in the forward;
+//   * row statistics (centred: per-wave mean and centred sum of squares, pooled) / the two LayerNorm-backward row sums
+//     cross the 4 waves through LDS, as in the forward;
 //   * dgamma' / dbeta' are reduced over a tile's 16 row lanes by shuffles and accumulated in LDS by the ONE lane
 //     that owns the column (deterministic), written once per workgroup at the end (persistent workgroups);
 //     the bias gradient (column sums of dz') comes out of hgnn_wgrad_bf16 (colsum) instead.
@@ -215,25 +216,34 @@ __global__ __launch_bounds__(NW * 64, MINB) void k_mlp_bwd_layer(const Args a) {
 #pragma unroll
                     for (int t = 0; t < NT; ++t) zr[t][j] = zload(t, j);
             }
+            // centred statistics, one exchange: the wave's own mean m_w and M2_w = sum((z - m_w)^2) over its NT * 16
+            // features; pooled below as mean = avg(m_w), M2 = sum(M2_w) + n_w sum((m_w - mean)^2)  (var >= 0 by construction)
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                float s = 0.f, q = 0.f;
+                float s = 0.f;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     const f32x4 x = cvt4(KEEPZ ? zr[KEEPZ ? t : 0][KEEPZ ? j : 0] : zload(t, j));
                     s += (x.x + x.y) + (x.z + x.w);
-                    q = fmaf(x.x, x.x, q);
-                    q = fmaf(x.y, x.y, q);
-                    q = fmaf(x.z, x.z, q);
-                    q = fmaf(x.w, x.w, q);
                 }
                 s += __shfl_xor(s, 16);
-                q += __shfl_xor(q, 16);
                 s += __shfl_xor(s, 32);
+                const float m = s * (1.0f / (float)(NT * 16));
+                float q = 0.f;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const f32x4 x = cvt4(KEEPZ ? zr[KEEPZ ? t : 0][KEEPZ ? j : 0] : zload(t, j));
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const float d = x[c] - m;
+                        q = fmaf(d, d, q);
+                    }
+                }
+                q += __shfl_xor(q, 16);
                 q += __shfl_xor(q, 32);
                 if (g == 0) {
                     f32x2 sq;
-                    sq.x = s;
+                    sq.x = m;
                     sq.y = q;
                     *(f32x2*)(red + (wave * TE + j * 16 + ei) * 2) = sq;
                 }
@@ -245,15 +255,22 @@ __global__ __launch_bounds__(NW * 64, MINB) void k_mlp_bwd_layer(const Args a) {
             float mean[NJ], rstd[NJ];
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                float s = 0.f, q = 0.f;
+                float mw[NW], s = 0.f, q = 0.f;
 #pragma unroll
                 for (int w = 0; w < NW; ++w) {
                     const f32x2 sq = *(const f32x2*)(red + (w * TE + j * 16 + ei) * 2);
+                    mw[w] = sq.x;
                     s += sq.x;
                     q += sq.y;
                 }
-                mean[j] = s * inv_n;
-                const float var = fmaxf(fmaf(-mean[j], mean[j], q * inv_n), 0.f);
+                mean[j] = s * (1.0f / (float)NW);
+                float c = 0.f;
+#pragma unroll
+                for (int w = 0; w < NW; ++w) {
+                    const float d = mw[w] - mean[j];
+                    c = fmaf(d, d, c);
+                }
+                const float var = fmaf(c, (float)(NT * 16), q) * inv_n;
                 rstd[j] = 1.0f / sqrtf(var + a.eps);
             }
             __syncthreads();  // everyone has read the statistics: `red` is free for the second exchange

@@ -8,7 +8,8 @@
 // costs 3 bf16 MFMAs = 3/16 of the time of the one fp32 MFMA (v_mfma_f32_16x16x4_f32 runs at 1/16 of the bf16 rate).
 // Error budget, measured against the REFERENCE's scores on BASELINE config 2 (tests/test_split_bf16_study.py, oracle
 // arithmetic): 2.0e-5 at model level, 5x inside the 1e-4 bar; bias, LayerNorm, activations (exact-erf GELU), skip and
-// all rows in HBM stay fp32.
+// all rows in HBM stay fp32.  LayerNorm statistics are CENTRED (no E[z^2] - mean^2 cancellation): each wave's mean and
+// centred sum of squares over its own features, pooled across the waves after one LDS exchange; (z - mean) * rstd.
 //
 // Decomposition = the bf16 feature-split kernel's (mlp_split_bf16.hip): a workgroup of 8 waves owns 64 rows, wave w an
 // eighth of every layer's features; weights stream from L2 in A-fragment order through the register ring (gemm_lds).
@@ -93,45 +94,62 @@ __device__ __forceinline__ void layernorm_act(f32x4 (&acc)[NT][NJ], const float*
                                               const float* __restrict__ lnb, int act_rt, float eps, float* red, int wave,
                                               int ei, int g) {
     const int act = ACT >= 0 ? ACT : act_rt;
+    // Row statistics without cancellation: every wave centres its own NT * 16 features on their own mean (m_w, M2_w =
+    // sum of squared deviations from m_w), ONE exchange through LDS as before, and the waves' pairs are pooled:
+    //     mean = avg(m_w),   M2 = sum(M2_w) + n_w sum((m_w - mean)^2)      (all terms >= 0: var >= 0 by construction)
     constexpr float inv_n = 1.0f / (float)(NW * NT * 16);
+    constexpr float inv_nw = 1.0f / (float)(NT * 16);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-        float s = 0.f, q = 0.f;
+        float s = 0.f;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const f32x4 v = acc[t][j];
             s += (v.x + v.y) + (v.z + v.w);
-            q = fmaf(v.x, v.x, q);
-            q = fmaf(v.y, v.y, q);
-            q = fmaf(v.z, v.z, q);
-            q = fmaf(v.w, v.w, q);
         }
         s += __shfl_xor(s, 16);
-        q += __shfl_xor(q, 16);
         s += __shfl_xor(s, 32);
+        const float m = s * inv_nw;
+        float q = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const f32x4 v = acc[t][j];
+            const float dx = v.x - m, dy = v.y - m, dz = v.z - m, dw = v.w - m;
+            q = fmaf(dx, dx, q);
+            q = fmaf(dy, dy, q);
+            q = fmaf(dz, dz, q);
+            q = fmaf(dw, dw, q);
+        }
+        q += __shfl_xor(q, 16);
         q += __shfl_xor(q, 32);
         if (g == 0) {
             f32x2 sq;
-            sq.x = s;
+            sq.x = m;
             sq.y = q;
             *(f32x2*)(red + (wave * TE + j * 16 + ei) * 2) = sq;
         }
     }
     __syncthreads();
-    float rstd[NJ], shift[NJ];
+    float rstd[NJ], mean[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-        float s = 0.f, q = 0.f;
+        float mw[NW], s = 0.f, q = 0.f;
 #pragma unroll
         for (int w = 0; w < NW; ++w) {
             const f32x2 sq = *(const f32x2*)(red + (w * TE + j * 16 + ei) * 2);
+            mw[w] = sq.x;
             s += sq.x;
             q += sq.y;
         }
-        const float mean = s * inv_n;
-        const float var = fmaxf(fmaf(-mean, mean, q * inv_n), 0.f);
+        mean[j] = s * (1.0f / (float)NW);
+        float c = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float d = mw[w] - mean[j];
+            c = fmaf(d, d, c);
+        }
+        const float var = fmaf(c, (float)(NT * 16), q) * inv_n;
         rstd[j] = 1.0f / sqrtf(var + eps);
-        shift[j] = -mean * rstd[j];
     }
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -140,10 +158,10 @@ __device__ __forceinline__ void layernorm_act(f32x4 (&acc)[NT][NJ], const float*
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             f32x4 v = acc[t][j];
-            v.x = act_apply(fmaf(fmaf(v.x, rstd[j], shift[j]), w4.x, b4.x), act);
-            v.y = act_apply(fmaf(fmaf(v.y, rstd[j], shift[j]), w4.y, b4.y), act);
-            v.z = act_apply(fmaf(fmaf(v.z, rstd[j], shift[j]), w4.z, b4.z), act);
-            v.w = act_apply(fmaf(fmaf(v.w, rstd[j], shift[j]), w4.w, b4.w), act);
+            v.x = act_apply(fmaf((v.x - mean[j]) * rstd[j], w4.x, b4.x), act);
+            v.y = act_apply(fmaf((v.y - mean[j]) * rstd[j], w4.y, b4.y), act);
+            v.z = act_apply(fmaf((v.z - mean[j]) * rstd[j], w4.z, b4.z), act);
+            v.w = act_apply(fmaf((v.w - mean[j]) * rstd[j], w4.w, b4.w), act);
             acc[t][j] = v;
         }
     }
@@ -260,7 +278,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_mlp_f32_split3(con
     constexpr int PHB = H * 4;                 // bytes of an fp32 P row
     constexpr int REGION = cmax(cmax(2 * PLB, 4 * PANEL), 4 * 16 * PHB);
     constexpr int NC = H / 32;                 // k-chunks of a hidden layer (per plane)
-    float* red = (float*)(smem + REGION);                 // [NW][TE][sum, sumsq]
+    float* red = (float*)(smem + REGION);                 // [NW][TE][wave mean, wave centred M2]
     int32_t* pidx = (int32_t*)(red + NW * TE * 2);        // [2][TE]
     int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);

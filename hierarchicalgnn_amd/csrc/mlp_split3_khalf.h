@@ -80,43 +80,54 @@ __device__ __forceinline__ void gemm3w(f32x4 (&acc)[NT][WNJ], const u16x8* __res
 
 template <int NT, int NWV, int ACT>
 __device__ __forceinline__ void ln_stats(const f32x4 (&acc)[NT][WNJ], float eps, float* red, int wave, int ei, int g,
-                                         float (&rstd)[WNJ], float (&shift)[WNJ]) {
+                                         float (&rstd)[WNJ], float (&mean)[WNJ]) {
+    // centred statistics with ONE exchange (as in the 64-row kernel): a wave writes the mean m_w of its own NT * 16 features
+    // and M2_w = sum((z - m_w)^2); pooled:  mean = avg(m_w),  M2 = sum(M2_w) + n_w sum((m_w - mean)^2)  -- var >= 0 by construction
     constexpr float inv_n = 1.0f / (float)(NWV * NT * 16);
+    constexpr float inv_nw = 1.0f / (float)(NT * 16);
 #pragma unroll
     for (int j = 0; j < WNJ; ++j) {
-        float s = 0.f, q = 0.f;
+        float s = 0.f;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const f32x4 v = acc[t][j];
             s += (v.x + v.y) + (v.z + v.w);
-            q = fmaf(v.x, v.x, q);
-            q = fmaf(v.y, v.y, q);
-            q = fmaf(v.z, v.z, q);
-            q = fmaf(v.w, v.w, q);
         }
         s += __shfl_xor(s, 16);
-        q += __shfl_xor(q, 16);
         s += __shfl_xor(s, 32);
+        const float m = s * inv_nw;
+        float q = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const f32x4 v = acc[t][j];
+            const float dx = v.x - m, dy = v.y - m, dz = v.z - m, dw = v.w - m;
+            q = fmaf(dx, dx, q);
+            q = fmaf(dy, dy, q);
+            q = fmaf(dz, dz, q);
+            q = fmaf(dw, dw, q);
+        }
+        q += __shfl_xor(q, 16);
         q += __shfl_xor(q, 32);
         if (g == 0) {
             f32x2 sq;
-            sq.x = s;
+            sq.x = m;
             sq.y = q;
             *(f32x2*)(red + (wave * WTE + j * 16 + ei) * 2) = sq;
         }
     }
     __syncthreads();
-    // Two stages.  Every lane summing its 8 rows over the 8 waves itself is 64 LDS reads in flight (128 registers: hipcc
-    // spilled the prefetched skip rows for them) and 8 divisions + square roots per lane.  Instead 4 threads reduce ONE row
-    // (2 waves' partials each, combined by lane shuffles), the first of them writes (rstd, shift) over the row's wave-0
-    // partial -- which only these 4 threads read -- and after a second barrier every lane reads its 8 rows' pairs.
+    // Two stages.  Every lane pooling its 8 rows over the 8 waves itself is 64 LDS reads in flight (128 registers: hipcc
+    // spilled the prefetched skip rows for them) and 8 divisions + square roots per lane.  Instead 4 threads pool ONE row
+    // (2 waves' pairs each, combined by lane shuffles), the first of them writes (rstd, mean) over the row's wave-0
+    // pair -- which only these 4 threads read -- and after a second barrier every lane reads its 8 rows' pairs.
     static_assert(NWV * 64 == 4 * WTE && NWV % 4 == 0, "4 threads per row");
     {
         const int row = (int)threadIdx.x >> 2, part = (int)threadIdx.x & 3;
-        float s = 0.f, q = 0.f;
+        float mw[NWV / 4], s = 0.f, q = 0.f;
 #pragma unroll
         for (int w = 0; w < NWV / 4; ++w) {
             const f32x2 sq = *(const f32x2*)(red + ((part * (NWV / 4) + w) * WTE + row) * 2);
+            mw[w] = sq.x;
             s += sq.x;
             q += sq.y;
         }
@@ -124,11 +135,19 @@ __device__ __forceinline__ void ln_stats(const f32x4 (&acc)[NT][WNJ], float eps,
         q += __shfl_xor(q, 1);
         s += __shfl_xor(s, 2);
         q += __shfl_xor(q, 2);
-        const float mean = s * inv_n;
-        const float var = fmaxf(fmaf(-mean, mean, q * inv_n), 0.f);
+        const float mean = s * (1.0f / (float)NWV);
+        float c = 0.f;
+#pragma unroll
+        for (int w = 0; w < NWV / 4; ++w) {
+            const float d = mw[w] - mean;
+            c = fmaf(d, d, c);
+        }
+        c += __shfl_xor(c, 1);
+        c += __shfl_xor(c, 2);
+        const float var = fmaf(c, (float)(NT * 16), q) * inv_n;
         f32x2 rs;
         rs.x = 1.0f / sqrtf(var + eps);
-        rs.y = -mean * rs.x;
+        rs.y = mean;
         if (part == 0) *(f32x2*)(red + row * 2) = rs;
     }
     __syncthreads();
@@ -136,18 +155,18 @@ __device__ __forceinline__ void ln_stats(const f32x4 (&acc)[NT][WNJ], float eps,
     for (int j = 0; j < WNJ; ++j) {
         const f32x2 rs = *(const f32x2*)(red + (j * 16 + ei) * 2);
         rstd[j] = rs.x;
-        shift[j] = rs.y;
+        mean[j] = rs.y;
     }
 }
 
 // LayerNorm (given the row statistics) + activation of ONE accumulator tile value (4 features of one row)
 template <int ACT>
-__device__ __forceinline__ f32x4 ln_act4(f32x4 v, float rs, float sh, const f32x4 w4, const f32x4 b4, int act_rt) {
+__device__ __forceinline__ f32x4 ln_act4(f32x4 v, float rs, float mu, const f32x4 w4, const f32x4 b4, int act_rt) {
     const int act = ACT >= 0 ? ACT : act_rt;
-    v.x = act_apply(fmaf(fmaf(v.x, rs, sh), w4.x, b4.x), act);
-    v.y = act_apply(fmaf(fmaf(v.y, rs, sh), w4.y, b4.y), act);
-    v.z = act_apply(fmaf(fmaf(v.z, rs, sh), w4.z, b4.z), act);
-    v.w = act_apply(fmaf(fmaf(v.w, rs, sh), w4.w, b4.w), act);
+    v.x = act_apply(fmaf((v.x - mu) * rs, w4.x, b4.x), act);
+    v.y = act_apply(fmaf((v.y - mu) * rs, w4.y, b4.y), act);
+    v.z = act_apply(fmaf((v.z - mu) * rs, w4.z, b4.z), act);
+    v.w = act_apply(fmaf((v.w - mu) * rs, w4.w, b4.w), act);
     return v;
 }
 
@@ -156,14 +175,14 @@ __device__ __forceinline__ f32x4 ln_act4(f32x4 v, float rs, float sh, const f32x
 template <int T0, int ACT>
 __device__ __forceinline__ void act_write_half(const f32x4 (&acc)[WNTH][WNJ], const float* __restrict__ lnw,
                                                const float* __restrict__ lnb, int act_rt, const float (&rstd)[WNJ],
-                                               const float (&shift)[WNJ], char* lane0) {
+                                               const float (&mean)[WNJ], char* lane0) {
 #pragma unroll
     for (int t = 0; t < WNTH / 2; ++t) {
         const f32x4 w4 = *(const f32x4*)(lnw + (T0 + t) * 16);
         const f32x4 b4 = *(const f32x4*)(lnb + (T0 + t) * 16);
 #pragma unroll
         for (int j = 0; j < WNJ; ++j) {
-            const f32x4 v = ln_act4<ACT>(acc[T0 + t][j], rstd[j], shift[j], w4, b4, act_rt);
+            const f32x4 v = ln_act4<ACT>(acc[T0 + t][j], rstd[j], mean[j], w4, b4, act_rt);
             u16x4 h, m;
             split4(v, h, m);
             *(u16x4*)(lane0 + j * 16 * WHRS + t * 32) = h;
@@ -372,8 +391,8 @@ __global__ __launch_bounds__(WNW * 64, 2) void k_mlp_f32_split3_khalf(const Args
                 }
             }
         }
-        float rstd[WNJ], shift[WNJ];
-        ln_stats<WNTH, WNW, ACT_H>(acc1, a.eps, red, wave, ei, g, rstd, shift);
+        float rstd[WNJ], mean[WNJ];
+        ln_stats<WNTH, WNW, ACT_H>(acc1, a.eps, red, wave, ei, g, rstd, mean);
         HGNN_STAMPW(4);
         // (the barrier inside also means: every wave is done reading the panels)
 
@@ -383,7 +402,7 @@ __global__ __launch_bounds__(WNW * 64, 2) void k_mlp_f32_split3_khalf(const Args
         const char* hlane = smem + ei * WHRS + (g << 4);
         int r_next[NIX];
         // half 0: tiles 0-1 of every wave = hidden features 64 w + [0, 32) = stream chunk 2 w
-        act_write_half<0, ACT_H>(acc1, a.lnw[0] + wave * WNTH * 16 + 4 * g, a.lnb[0] + wave * WNTH * 16 + 4 * g, a.act[0], rstd, shift, smem + ei * WHRS + wave * (WNTH * 16) + (g << 3));
+        act_write_half<0, ACT_H>(acc1, a.lnw[0] + wave * WNTH * 16 + 4 * g, a.lnb[0] + wave * WNTH * 16 + 4 * g, a.act[0], rstd, mean, smem + ei * WHRS + wave * (WNTH * 16) + (g << 3));
         __syncthreads();
         HGNN_STAMPW(5);
         f32x4 acc2[WNTO][WNJ];
@@ -405,14 +424,14 @@ __global__ __launch_bounds__(WNW * 64, 2) void k_mlp_f32_split3_khalf(const Args
         // the row statistics are re-read from LDS (still there: the next statistics pass comes after the output GEMM) instead
         // of living in 16 registers across the first half's GEMM -- hipcc spilled them (0.5 GB of scratch writes per launch)
         refresh();
-        float rstd_b[WNJ], shift_b[WNJ];
+        float rstd_b[WNJ], mean_b[WNJ];
 #pragma unroll
         for (int j = 0; j < WNJ; ++j) {
             const f32x2 rs = *(const f32x2*)(red + (j * 16 + ei) * 2);
             rstd_b[j] = rs.x;
-            shift_b[j] = rs.y;
+            mean_b[j] = rs.y;
         }
-        act_write_half<WNTH / 2, ACT_H>(acc1, a.lnw[0] + wave * WNTH * 16 + 4 * g, a.lnb[0] + wave * WNTH * 16 + 4 * g, a.act[0], rstd_b, shift_b, smem + ei * WHRS + wave * (WNTH * 16) + (g << 3));
+        act_write_half<WNTH / 2, ACT_H>(acc1, a.lnw[0] + wave * WNTH * 16 + 4 * g, a.lnb[0] + wave * WNTH * 16 + 4 * g, a.act[0], rstd_b, mean_b, smem + ei * WHRS + wave * (WNTH * 16) + (g << 3));
         __syncthreads();
         HGNN_STAMPW(7);
         gemm3w<WNTO, WHRS>(acc2, wpo, [](int s) { return 2 * ((s / WCW) * 2 * WCW + WCW + s % WCW); }, hlane, hlane + WPLB, 8);
@@ -457,8 +476,8 @@ __global__ __launch_bounds__(WNW * 64, 2) void k_mlp_f32_split3_khalf(const Args
 #pragma unroll
                 for (int t = 0; t < WNTO; ++t) sk[j][t] = *(const f32x4*)(a.skip + row_off(j) + t * 16);
         }
-        float rstd2[WNJ], shift2[WNJ];
-        ln_stats<WNTO, WNW, ACT_O>(acc2, a.eps, red, wave, ei, g, rstd2, shift2);
+        float rstd2[WNJ], mean2[WNJ];
+        ln_stats<WNTO, WNW, ACT_O>(acc2, a.eps, red, wave, ei, g, rstd2, mean2);
         // (the barriers inside: every wave is past the hidden planes, the next tile's indices are visible)
         if (has_next && npass > 0) {
             pissue(0, ti_next);
@@ -475,7 +494,7 @@ __global__ __launch_bounds__(WNW * 64, 2) void k_mlp_f32_split3_khalf(const Args
             const size_t o = row_off(j);
 #pragma unroll
             for (int t = 0; t < WNTO; ++t) {
-                f32x4 v = ln_act4<ACT_O>(acc2[t][j], rstd2[j], shift2[j], w2[t], b2[t], a.act[LO]);
+                f32x4 v = ln_act4<ACT_O>(acc2[t][j], rstd2[j], mean2[j], w2[t], b2[t], a.act[LO]);
                 if (a.skip != nullptr) v += sk[j % SKD][t];
                 if (ok) *(f32x4*)(a.out + o + t * 16) = v;
             }

@@ -15,7 +15,8 @@
 //     128-wide k-panels (coalesced 256-byte row pieces, double-buffered), and the hidden activations of each
 //     layer as bf16 [64][H] (padded rows: conflict-free ds_write_b64 / ds_read_b128);
 //   * LayerNorm statistics: in-register partial sums over the wave's features, exchanged through
-//     LDS (2 floats per edge per wave), one-pass variance in fp32.
+//     LDS (2 floats per edge per wave: the wave's own mean and its centred sum of squares), pooled in fp32 --
+//     centred variance, (z - mean) * rstd.
 // GEMMs are transposed as in the other kernels (A = W fragment, B = activations, D[f][e]): lane
 // (e = lane&15, g = lane>>4) holds features 16T + 4g + r of edge 16j + e.
 #include "mlp_split_common.h"
@@ -61,44 +62,60 @@ __device__ __forceinline__ void layernorm_act(f32x4 (&acc)[NT][NJ], const float*
         __syncthreads();
         return;
     }
+    // centred statistics, one exchange: wave-local mean m_w and M2_w = sum((z - m_w)^2), pooled over the waves as
+    // mean = avg(m_w), M2 = sum(M2_w) + n_w sum((m_w - mean)^2)  (every term >= 0, no cancellation)
+    constexpr float inv_nw = 1.0f / (float)(NT * 16);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-        float s = 0.f, q = 0.f;
+        float s = 0.f;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const f32x4 v = acc[t][j];
             s += (v.x + v.y) + (v.z + v.w);
-            q = fmaf(v.x, v.x, q);
-            q = fmaf(v.y, v.y, q);
-            q = fmaf(v.z, v.z, q);
-            q = fmaf(v.w, v.w, q);
         }
         s += __shfl_xor(s, 16);
-        q += __shfl_xor(q, 16);
         s += __shfl_xor(s, 32);
+        const float m = s * inv_nw;
+        float q = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const f32x4 v = acc[t][j];
+            const float dx = v.x - m, dy = v.y - m, dz = v.z - m, dw = v.w - m;
+            q = fmaf(dx, dx, q);
+            q = fmaf(dy, dy, q);
+            q = fmaf(dz, dz, q);
+            q = fmaf(dw, dw, q);
+        }
+        q += __shfl_xor(q, 16);
         q += __shfl_xor(q, 32);
         if (g == 0) {
             f32x2 sq;
-            sq.x = s;
+            sq.x = m;
             sq.y = q;
             *(f32x2*)(red + (wave * TE + j * 16 + ei) * 2) = sq;
         }
     }
     __syncthreads();
-    float rstd[NJ], shift[NJ];
+    float rstd[NJ], mean[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-        float s = 0.f, q = 0.f;
+        float mw[NW], s = 0.f, q = 0.f;
 #pragma unroll
         for (int w = 0; w < NW; ++w) {
             const f32x2 sq = *(const f32x2*)(red + (w * TE + j * 16 + ei) * 2);
+            mw[w] = sq.x;
             s += sq.x;
             q += sq.y;
         }
-        const float mean = s * inv_n;
-        const float var = fmaxf(fmaf(-mean, mean, q * inv_n), 0.f);
+        mean[j] = s * (1.0f / (float)NW);
+        float c = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float d = mw[w] - mean[j];
+            c = fmaf(d, d, c);
+        }
+        const float var = fmaf(c, (float)(NT * 16), q) * inv_n;
         rstd[j] = 1.0f / sqrtf(var + eps);
-        shift[j] = -mean * rstd[j];
     }
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -107,10 +124,10 @@ __device__ __forceinline__ void layernorm_act(f32x4 (&acc)[NT][NJ], const float*
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             f32x4 v = acc[t][j];
-            v.x = act_t<ACT>(fmaf(fmaf(v.x, rstd[j], shift[j]), w4.x, b4.x), act);
-            v.y = act_t<ACT>(fmaf(fmaf(v.y, rstd[j], shift[j]), w4.y, b4.y), act);
-            v.z = act_t<ACT>(fmaf(fmaf(v.z, rstd[j], shift[j]), w4.z, b4.z), act);
-            v.w = act_t<ACT>(fmaf(fmaf(v.w, rstd[j], shift[j]), w4.w, b4.w), act);
+            v.x = act_t<ACT>(fmaf((v.x - mean[j]) * rstd[j], w4.x, b4.x), act);
+            v.y = act_t<ACT>(fmaf((v.y - mean[j]) * rstd[j], w4.y, b4.y), act);
+            v.z = act_t<ACT>(fmaf((v.z - mean[j]) * rstd[j], w4.z, b4.z), act);
+            v.w = act_t<ACT>(fmaf((v.w - mean[j]) * rstd[j], w4.w, b4.w), act);
             acc[t][j] = v;
         }
     }
