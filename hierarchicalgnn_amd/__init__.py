@@ -12,6 +12,7 @@ Drop-in surface (same names / signatures as the reference):
     pair_hinge_loss(...), embedding_hgnn_training_loss(...)   <- EmbeddingBase.training_step's weighted hinge loss
     weighted_bce_loss(...), ec_training_loss(...), ec_shared_evaluation(...)   <- EdgeClassifierBase.training_step / shared_evaluation
     hdbscan(points, min_cluster_size), embedding_track_candidates(...)   <- cuml.cluster.HDBSCAN (embedding validation)
+    FusedAdamW(params, lr, ...), configure_optimizers(...), optimizer_step(...)   <- Trainer(gradient_clip_val) + AdamW(amsgrad) of every base
 
 Everything on the hot path runs in hand-written HIP kernels loaded from
 libhgnn_hip.so through the C ABI of include/hgnn_hip.h; there is no CPU or
@@ -33,5 +34,6 @@ from .assignment import (max_weight_matching, bipartite_loss, bc_embedding_loss,
                          gap_bound)
 from .edge_classifier import (weighted_bce_loss, weighted_bce_check, ec_training_loss,  # noqa: F401
                               ec_shared_evaluation)
+from .optim import FusedAdamW, configure_optimizers, optimizer_step  # noqa: F401
 
 __version__ = "0.1.0"

@@ -47,6 +47,12 @@ WB_COMBINE_SUM, WB_COMBINE_MAX = 0, 1
 WB_ST_BAD_ID, WB_ST_BAD_SCORE = 1, 2
 WB_KT, WB_KF, WB_ST, WB_SF, WB_LOSS = range(5)
 WB_STATE = 8
+# HGNN_OPT_*: hgnn_optim_*'s chunk size, flag bits, status bit and device state vector
+OPT_CHUNK = 4096
+OPT_AMSGRAD, OPT_CLIP, OPT_ZERO_GRADS, OPT_WRITE_GRADS, OPT_SCALAR = 1, 2, 4, 8, 16
+OPT_ST_NONFINITE = 1
+OPT_NORM, OPT_COEF, OPT_SUMSQ = range(3)
+OPT_STATE = 4
 
 class HgnnPlan(Structure):
     """mirror of ``struct hgnn_plan``"""
@@ -76,6 +82,15 @@ class HgnnMlpDesc(Structure):
         ("save_pre", c_void_p * 3),
         ("n_pre", c_int32),
         ("pre_table", c_void_p * 2), ("pre_index", c_void_p * 2),
+    ]
+
+
+class HgnnOptEntry(Structure):
+    """mirror of ``struct hgnn_opt_entry``"""
+    _fields_ = [
+        ("p", c_void_p), ("g", c_void_p), ("offset", c_int64), ("numel", c_int64), ("first_chunk", c_int64),
+        ("decay", c_float), ("step_size", c_float), ("inv_sqrt_bc2", c_float), ("one_minus_b1", c_float),
+        ("b2", c_float), ("one_minus_b2", c_float), ("eps", c_float), ("reserved", c_int32),
     ]
 
 
@@ -176,6 +191,12 @@ _SIGNATURES = {
     "hgnn_weighted_bce_backward": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                            c_int64, c_int64, c_int32, POINTER(c_double), c_void_p, c_void_p, c_void_p,
                                            c_void_p]),
+    "hgnn_sizeof_opt_entry": (c_int, []),
+    "hgnn_optim_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
+    "hgnn_optim_grad_norm": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_int32, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
+    "hgnn_optim_adamw_step": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None

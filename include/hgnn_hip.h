@@ -52,7 +52,8 @@ extern "C" {
 
 /* hgnn_assign_match and hgnn_assign_match_workspace_bytes were added without a bump: they are additions, and
  * no existing entry point, struct or constant changed layout or meaning.  The same holds for
- * hgnn_segment_reduce_f32_ex, hgnn_plan_item_order(_workspace_bytes) and hgnn_get_option. */
+ * hgnn_segment_reduce_f32_ex, hgnn_plan_item_order(_workspace_bytes), hgnn_get_option and the optimiser step
+ * (hgnn_optim_*, hgnn_sizeof_opt_entry, struct hgnn_opt_entry, HGNN_OPT_*). */
 #define HGNN_ABI_VERSION 26
 
 typedef void* hgnn_stream_t; /* hipStream_t */
@@ -738,6 +739,65 @@ int hgnn_weighted_bce_backward(const float* scores, const void* graph, int32_t i
                                const uint8_t* keep, const float* pt_a, int64_t NA, const float* pt_b, int64_t NB,
                                int64_t P, int32_t combine, const double* hparams, const double* state,
                                const float* grad_out, float* grad_scores, hgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * The optimiser step of the training bases as one operator: clip_grad_norm_(max_norm) over all gradients, then
+ * torch.optim.AdamW (decoupled weight decay, amsgrad or not), then optionally zero_grad (reference
+ * Modules/.../..._base.py configure_optimizers, Trainer(gradient_clip_val)).  Added under ABI 26: additions only.
+ *
+ * The tensors of one step are described by a table of hgnn_opt_entry, one per parameter that has a gradient, given
+ * twice: host_table (HOST memory, read and checked before the call returns) and table (the same bytes in DEVICE
+ * memory, read by the kernels).  p and g are float32 device arrays of numel elements, 4-byte aligned; the tensor's
+ * exp_avg, exp_avg_sq and max_exp_avg_sq are the elements [offset, offset + numel) of three flat float32 buffers of
+ * state_numel elements each.  The work is cut into chunks of HGNN_OPT_CHUNK consecutive elements of one tensor;
+ * first_chunk is the number of chunks of the entries before this one (entry i owns ceil(numel_i / HGNN_OPT_CHUNK)
+ * chunks) and n_chunks their total.  Tensors whose p, g and offset are 16-byte aligned are moved in 16-byte words,
+ * others and tails element by element; both give the same bits.  The scalars are this step's, per tensor, rounded
+ * from double:
+ *     decay = 1 - lr wd, step_size = lr / (1 - b1^t), inv_sqrt_bc2 = 1 / sqrt(1 - b2^t), one_minus_b1, b2,
+ *     one_minus_b2, eps
+ * Per element, float32, every operation rounded on its own ("k_opt"):
+ *     g' = g coef;  p *= decay;  m += (g' - m) one_minus_b1;  v = v b2 + (one_minus_b2 g') g';  vmax = max(vmax, v);
+ *     p -= step_size (m / (sqrt(vmax) inv_sqrt_bc2 + eps))            (v for vmax without HGNN_OPT_AMSGRAD)
+ * hgnn_optim_grad_norm: state device double[HGNN_OPT_STATE]: total_norm = sqrt(sum g^2) (a float64 sum in a fixed
+ *   order that depends on the tensor sizes alone: two calls give the same bits), coef = min(1, max_norm /
+ *   (total_norm + 1e-6)) formed in float32 (NaN stays NaN), and the sum.  status device int32[1]: HGNN_OPT_ST_NONFINITE
+ *   is OR-ed into it when total_norm is inf or NaN; the call never clears it.  flags: 0 or HGNN_OPT_SCALAR.
+ * hgnn_optim_adamw_step: flags = OR of HGNN_OPT_AMSGRAD, HGNN_OPT_CLIP (g' = g state[HGNN_OPT_COEF]; without it
+ *   state may be NULL and g' = g), HGNN_OPT_ZERO_GRADS (0 is stored to g after it is read), HGNN_OPT_WRITE_GRADS (g'
+ *   is stored to g: the in-place clip; excludes ZERO_GRADS), HGNN_OPT_SCALAR (no 16-byte accesses).  The three state
+ *   buffers must be 16-byte aligned; max_exp_avg_sq may be NULL without HGNN_OPT_AMSGRAD.  One launch.
+ * Both launch asynchronously, allocate nothing, never synchronise and read nothing back.
+ * hgnn_optim_workspace_bytes: device scratch of hgnn_optim_grad_norm (independent of n_chunks).
+ * ------------------------------------------------------------------------ */
+#define HGNN_OPT_CHUNK 4096
+#define HGNN_OPT_AMSGRAD 1
+#define HGNN_OPT_CLIP 2
+#define HGNN_OPT_ZERO_GRADS 4
+#define HGNN_OPT_WRITE_GRADS 8
+#define HGNN_OPT_SCALAR 16
+#define HGNN_OPT_ST_NONFINITE 1
+#define HGNN_OPT_NORM 0
+#define HGNN_OPT_COEF 1
+#define HGNN_OPT_SUMSQ 2
+#define HGNN_OPT_STATE 4
+typedef struct hgnn_opt_entry {
+    float* p;
+    float* g;
+    int64_t offset;
+    int64_t numel;
+    int64_t first_chunk;
+    float decay, step_size, inv_sqrt_bc2, one_minus_b1, b2, one_minus_b2, eps;
+    int32_t reserved;
+} hgnn_opt_entry;
+int hgnn_sizeof_opt_entry(void);
+int hgnn_optim_workspace_bytes(int64_t n_chunks, size_t* bytes);
+int hgnn_optim_grad_norm(const hgnn_opt_entry* host_table, const hgnn_opt_entry* table, int64_t n_tensors,
+                         int64_t n_chunks, double max_norm, int32_t flags, double* state, int32_t* status,
+                         void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
+int hgnn_optim_adamw_step(const hgnn_opt_entry* host_table, const hgnn_opt_entry* table, int64_t n_tensors,
+                          int64_t n_chunks, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                          int64_t state_numel, int32_t flags, const double* state, hgnn_stream_t stream);
 
 #ifdef __cplusplus
 }
