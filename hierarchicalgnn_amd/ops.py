@@ -569,6 +569,18 @@ def knn_radius_stats():
     return int(v), int(s)
 
 
+def _wgrad_operand(t: torch.Tensor) -> torch.Tensor:
+    """an operand of the weight-gradient kernels as they can read it: 16-byte pieces of row-major rows.  A view with a
+    column stride, with a row stride that is no multiple of 16 bytes, or whose first element is not 16-byte aligned (a
+    column slice at such an offset) is copied; every other column slice is read in place."""
+    per16 = 16 // t.element_size()
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) % per16):
+        t = t.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
 def wgrad_bf16(dz: torch.Tensor, rows: torch.Tensor, out: Optional[torch.Tensor] = None,
                colsum: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``dz^T @ rows`` for bf16 ``dz[M, Ho]`` and ``rows[M, Hi]`` (row-major, possibly column slices of wider
@@ -580,10 +592,7 @@ def wgrad_bf16(dz: torch.Tensor, rows: torch.Tensor, out: Optional[torch.Tensor]
     if dz.dtype != torch.bfloat16 or rows.dtype != torch.bfloat16 or dz.dim() != 2 or rows.dim() != 2 \
             or dz.shape[0] != rows.shape[0]:
         raise RuntimeError("wgrad_bf16: bf16 dz[M, Ho] and rows[M, Hi] expected")
-    if dz.stride(1) != 1:
-        dz = dz.contiguous()
-    if rows.stride(1) != 1:
-        rows = rows.contiguous()
+    dz, rows = _wgrad_operand(dz), _wgrad_operand(rows)
     M, Ho, Hi = int(dz.shape[0]), int(dz.shape[1]), int(rows.shape[1])
     if out is None:
         out = torch.empty((Ho, Hi), dtype=torch.float32, device=dz.device)
@@ -615,10 +624,7 @@ def wgrad_f32_split3(dz: torch.Tensor, rows: torch.Tensor, out: Optional[torch.T
     if dz.dtype != torch.float32 or rows.dtype != torch.float32 or dz.dim() != 2 or rows.dim() != 2 \
             or dz.shape[0] != rows.shape[0]:
         raise RuntimeError("wgrad_f32_split3: fp32 dz[M, Ho] and rows[M, Hi] expected")
-    if dz.stride(1) != 1 or (dz.shape[0] > 1 and dz.stride(0) % 4) or dz.data_ptr() % 16:
-        dz = dz.contiguous()
-    if rows.stride(1) != 1 or (rows.shape[0] > 1 and rows.stride(0) % 4) or rows.data_ptr() % 16:
-        rows = rows.contiguous()
+    dz, rows = _wgrad_operand(dz), _wgrad_operand(rows)
     M, Ho, Hi = int(dz.shape[0]), int(dz.shape[1]), int(rows.shape[1])
     if out is None:
         out = torch.empty((Ho, Hi), dtype=torch.float32, device=dz.device)
