@@ -151,6 +151,8 @@ _SIGNATURES = {
                                              c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hgnn_mlp_supported": (c_int, [POINTER(HgnnMlpDesc)]),
     "hgnn_mlp_forward_f32": (c_int, [POINTER(HgnnMlpDesc), c_void_p, c_void_p]),
+    "hgnn_mlp_supported_f32_padded": (c_int, [POINTER(HgnnMlpDesc)]),
+    "hgnn_mlp_forward_f32_padded": (c_int, [POINTER(HgnnMlpDesc), c_void_p, c_void_p]),
     "hgnn_mlp_supported_bf16": (c_int, [POINTER(HgnnMlpDesc)]),
     "hgnn_mlp_forward_bf16": (c_int, [POINTER(HgnnMlpDesc), c_void_p, c_void_p]),
     "hgnn_mlp_supported_bf16_split": (c_int, [POINTER(HgnnMlpDesc)]),

@@ -30,6 +30,9 @@
 //   * small-K mode (encoders, K = 3 / 6) and width-1 plain last layers (heads) are
 //     handled by zero padding (see hgnn_mlp_desc in include/hgnn_hip.h); `save_pre`
 //     dumps the pre-LayerNorm outputs for the opt-in differentiable variant.
+//   * widths between the template grid's (PAD kernels, hgnn_mlp_forward_f32_padded): the next grid instantiation on
+//     zero-padded parameters; LayerNorm statistics masked to the real features, dumps / skip / stores at the real
+//     row widths.  PAD is false for every kernel of the native grid, whose device code does not depend on it.
 #include "mlp_common.h"
 #include "options.h"
 
@@ -61,6 +64,7 @@ struct MlpArgs {
     int n_pre;
     long long M;
     int ablate;        // DIAGNOSTIC ONLY (wrong results): 1 = skip LN/act, 2 = skip weight DMA, 4 = skip barriers
+    int real[3];       // PAD kernels only: real output width of every layer (<= its tile width; the rest is zero padding)
 };
 
 template <int NF, int NW>
@@ -74,28 +78,40 @@ __device__ __forceinline__ void stage_w(const float* __restrict__ W, int Kdim, i
 // acc[T][r] (edge = lane&15, feature = 16T + 4*(lane>>4) + r): LayerNorm over features, then act
 // PARTIAL: only n_real < NT*16 features are real; the padded ones have zero weights and bias, so their
 // accumulators are exactly 0: they add nothing to the sum and mean^2 each to the squared deviations
-template <int NT, int ACT, bool LN = true, bool PARTIAL = false>
+// MASK (the PAD kernels, any number of padded tiles): the padded features are left out of the centred pass instead
+// (n_real % 4 == 0: a lane's four features of a tile are all real or all padding), nothing is corrected afterwards --
+// at up to 7 padded tiles  pad * mean^2  cancels badly against q on a row with an offset.  Their ln_w / ln_b are
+// zero, so they come out as exactly 0 and feed zeros into the next layer.
+template <int NT, int ACT, bool LN = true, bool PARTIAL = false, bool MASK = false>
 __device__ __forceinline__ void layernorm_act(f32x4 (&acc)[NT], const float* __restrict__ lnw,
                                               const float* __restrict__ lnb, int act, float eps, int g,
                                               int n_real = NT * 16) {
+    static_assert(!(PARTIAL && MASK), "one treatment of the padded features");
     if (!LN) return;  // plain last layer of a head: bias only
-    const float inv_n = PARTIAL ? 1.0f / (float)n_real : 1.0f / (float)(NT * 16);
+    const float inv_n = (PARTIAL || MASK) ? 1.0f / (float)n_real : 1.0f / (float)(NT * 16);
     float s = 0.f;
 #pragma unroll
     for (int T = 0; T < NT; ++T) s += (acc[T].x + acc[T].y) + (acc[T].z + acc[T].w);
     s += __shfl_xor(s, 16);
     s += __shfl_xor(s, 32);
-    const float mean = s * inv_n;
+    // MASK: n_real is no power of two, 1 / n_real is rounded: a true division keeps the mean of a constant row exact
+    // (its deviations exactly 0), as s * 2^-k does on the grid widths
+    const float mean = MASK ? s / (float)n_real : s * inv_n;
     float q = 0.f;
 #pragma unroll
     for (int T = 0; T < NT; ++T) {
         f32x4 d = acc[T] - mean;
-        q += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+        if constexpr (MASK) {
+            const float t = (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+            q += (T * 16 + g * 4 < n_real) ? t : 0.f;
+        } else {
+            q += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+        }
     }
     q += __shfl_xor(q, 16);
     q += __shfl_xor(q, 32);
     if (PARTIAL) q -= (float)(NT * 16 - n_real) * mean * mean;
-    const float rstd = 1.0f / sqrtf(q * inv_n + eps);
+    const float rstd = 1.0f / sqrtf((MASK ? q / (float)n_real : q * inv_n) + eps);
 #pragma unroll
     for (int T = 0; T < NT; ++T) {
         const f32x4 w4 = *(const f32x4*)(lnw + T * 16 + g * 4);
@@ -218,11 +234,45 @@ __device__ __forceinline__ void store_out(const f32x4 (&acc)[NT], const MlpArgs&
     }
 }
 
+// PAD kernels: out[e][0 .. n_out_real) (+ skip rows of the same width), 16-byte pieces (n_out_real % 4 == 0)
+template <int NT>
+__device__ __forceinline__ void store_out_pad(const f32x4 (&acc)[NT], const MlpArgs& a, long long e, bool valid,
+                                              int g) {
+    if (!valid) return;
+    const int nr = a.n_out_real;
+    float* op = a.out + (size_t)e * (size_t)nr;
+    if (a.skip != nullptr) {
+        const float* sp = a.skip + (size_t)e * (size_t)nr;
+#pragma unroll
+        for (int T = 0; T < NT; ++T) {
+            const int col = T * 16 + g * 4;
+            if (col < nr) *(f32x4*)(op + col) = acc[T] + *(const f32x4*)(sp + col);
+        }
+    } else {
+#pragma unroll
+        for (int T = 0; T < NT; ++T) {
+            const int col = T * 16 + g * 4;
+            if (col < nr) *(f32x4*)(op + col) = acc[T];
+        }
+    }
+}
+
 // training: dump a layer's pre-LayerNorm activations z[e][f] (what the hand-written backward in
 // fused.py needs; the hidden activations themselves are recomputed from it, never stored)
-template <int NT>
-__device__ __forceinline__ void dump_pre(const f32x4 (&acc)[NT], float* base, long long e, bool valid, int g) {
+// PAD: rows of `real` floats (real % 4 == 0), the padded features are not written
+template <int NT, bool PAD = false>
+__device__ __forceinline__ void dump_pre(const f32x4 (&acc)[NT], float* base, long long e, bool valid, int g,
+                                         int real = NT * 16) {
     if (base == nullptr || !valid) return;  // base is wave-uniform
+    if constexpr (PAD) {
+        float* rp = base + (size_t)e * (size_t)real;
+#pragma unroll
+        for (int T = 0; T < NT; ++T) {
+            const int col = T * 16 + g * 4;
+            if (col < real) *(f32x4*)(rp + col) = acc[T];
+        }
+        return;
+    }
     float* op = base + (size_t)e * (NT * 16) + g * 4;
 #pragma unroll
     for (int T = 0; T < NT; ++T) *(f32x4*)(op + T * 16) = acc[T];
@@ -233,9 +283,13 @@ __device__ __forceinline__ void dump_pre(const f32x4 (&acc)[NT], float* base, lo
 // it from the descriptor per element (keeps rare combinations working without an instantiation)
 // PLAIN_LAST: the last layer has no LayerNorm / activation (classifier heads, width-1 output)
 // PARTIAL: the last layer's real width is a.n_out_real < its tile width (see MlpArgs)
+// PAD: EVERY layer's real width a.real[l] may be below its tile width (widths between the template grid's: weights,
+// biases and LayerNorm parameters zero padded, W[l >= 1] also in its columns); statistics are masked, dumps, skip
+// and stores use the real row strides.  False for every kernel of the native grid: their code does not depend on it.
 template <int NT1, int NT2, int NT3, int MINW, int ACT_H, int ACT_O, bool PLAIN_LAST = false, int NW = 4,
-          bool PARTIAL = false>
+          bool PARTIAL = false, bool PAD = false>
 __global__ __launch_bounds__(NW * 64, MINW) void k_fused_mlp(const MlpArgs a) {
+    static_assert(!PAD || (NT2 > 0 && PARTIAL == PLAIN_LAST), "PAD: 2 or 3 layers; heads keep the PARTIAL store");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -345,7 +399,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_fused_mlp(const MlpArgs a) {
     // epilogue would otherwise starve the co-resident workgroup's MFMA stream whenever it is the
     // older of the two.  Epilogues run at priority 0, MFMA loops at priority 2.
     __builtin_amdgcn_s_setprio(0);
-    dump_pre<NT1>(acc1, a.save_pre[0], e, valid, g);
+    dump_pre<NT1, PAD>(acc1, a.save_pre[0], e, valid, g, PAD ? a.real[0] : NT1 * 16);
     if constexpr (NT2 == 0) {
         // single-layer launch (fp32 at latent 512: a 1024-wide hidden layer is 256 accumulators per lane, so the
         // layers of an MLP run as separate launches and the hidden rows make one trip through HBM)
@@ -353,7 +407,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_fused_mlp(const MlpArgs a) {
         store_out<NT1>(acc1, a, e, valid, g);
         return;
     }
-    if (!(a.ablate & 1)) layernorm_act<NT1, ACT_H>(acc1, a.lnw[0], a.lnb[0], a.act[0], a.eps, g);
+    if (!(a.ablate & 1))
+        layernorm_act<NT1, ACT_H, true, false, PAD>(acc1, a.lnw[0], a.lnb[0], a.act[0], a.eps, g,
+                                                    PAD ? a.real[0] : NT1 * 16);
     __builtin_amdgcn_s_setprio(2);
 
     // ---------------- layer 2 (and 3): activations stay in registers
@@ -362,32 +418,35 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_fused_mlp(const MlpArgs a) {
     init_bias<N2>(acc2, a.b[1], g);
     dense_from_regs<NT1, N2, NW>(acc1, acc2, a.W[1], lds, wave, lane, a.ablate);
     __builtin_amdgcn_s_setprio(0);
-    dump_pre<N2>(acc2, a.save_pre[1], e, valid, g);
+    dump_pre<N2, PAD>(acc2, a.save_pre[1], e, valid, g, PAD ? a.real[1] : N2 * 16);
     if (!(a.ablate & 1))
-        layernorm_act<N2, (NT3 == 0 ? ACT_O : ACT_H), !(PLAIN_LAST && NT3 == 0), (PARTIAL && NT3 == 0)>(
-            acc2, a.lnw[1], a.lnb[1], a.act[1], a.eps, g, NT3 == 0 ? a.n_out_real : N2 * 16);
+        layernorm_act<N2, (NT3 == 0 ? ACT_O : ACT_H), !(PLAIN_LAST && NT3 == 0), (PARTIAL && NT3 == 0 && !PAD), PAD>(
+            acc2, a.lnw[1], a.lnb[1], a.act[1], a.eps, g, PAD ? a.real[1] : (NT3 == 0 ? a.n_out_real : N2 * 16));
     if constexpr (NT3 == 0) {
-        store_out<N2, PARTIAL>(acc2, a, e, valid, g);
+        if constexpr (PAD) store_out_pad<N2>(acc2, a, e, valid, g);
+        else store_out<N2, PARTIAL>(acc2, a, e, valid, g);
     } else {
         f32x4 acc3[NT3];
         init_bias<NT3>(acc3, a.b[2], g);
         __builtin_amdgcn_s_setprio(2);
         dense_from_regs<N2, NT3, NW>(acc2, acc3, a.W[2], lds, wave, lane, a.ablate);
         __builtin_amdgcn_s_setprio(0);
-        dump_pre<NT3>(acc3, a.save_pre[2], e, valid, g);
+        dump_pre<NT3, PAD>(acc3, a.save_pre[2], e, valid, g, PAD ? a.real[2] : NT3 * 16);
         if (!(a.ablate & 1))
-            layernorm_act<NT3, ACT_O, !PLAIN_LAST, PARTIAL>(acc3, a.lnw[2], a.lnb[2], a.act[2], a.eps, g, a.n_out_real);
-        store_out<NT3, PARTIAL>(acc3, a, e, valid, g);
+            layernorm_act<NT3, ACT_O, !PLAIN_LAST, (PARTIAL && !PAD), PAD>(acc3, a.lnw[2], a.lnb[2], a.act[2], a.eps, g,
+                                                                           a.n_out_real);
+        if constexpr (PAD && !PLAIN_LAST) store_out_pad<NT3>(acc3, a, e, valid, g);
+        else store_out<NT3, PARTIAL>(acc3, a, e, valid, g);
     }
 }
 
 template <int NT1, int NT2, int NT3, int MINW, int ACT_H, int ACT_O, bool PLAIN_LAST = false, int NW = 4,
-          bool PARTIAL = false>
+          bool PARTIAL = false, bool PAD = false>
 static int launch_mlp_act(const MlpArgs& a, hipStream_t s) {
     constexpr int maxnt = NT1 > NT2 ? (NT1 > NT3 ? NT1 : NT3) : (NT2 > NT3 ? NT2 : NT3);
     const size_t lds_bytes = (size_t)2 * maxnt * 256 * sizeof(float);
     const unsigned grid = (unsigned)ceil_div(a.M, NW * 16);
-    auto kern = k_fused_mlp<NT1, NT2, NT3, MINW, ACT_H, ACT_O, PLAIN_LAST, NW, PARTIAL>;
+    auto kern = k_fused_mlp<NT1, NT2, NT3, MINW, ACT_H, ACT_O, PLAIN_LAST, NW, PARTIAL, PAD>;
     if (lds_bytes > 64 * 1024) {
         HGNN_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)lds_bytes));
@@ -441,6 +500,35 @@ static int launch_head(const MlpArgs& a, hipStream_t s) {
     if (a.act[0] == HGNN_ACT_TANH && a.act[1] == HGNN_ACT_TANH)
         return launch_mlp_act<NTH, NTH, 2, MINW, HGNN_ACT_TANH, HGNN_ACT_NONE, true, 4, true>(a, s);
     return launch_mlp_act<NTH, NTH, 2, MINW, -1, HGNN_ACT_NONE, true, 4, true>(a, s);
+}
+
+// widths between the grid's (PAD kernels): the instantiation of the next grid width P, see hgnn_mlp_supported_f32_padded
+template <int NT1, int NT2, int NT3, int MINW>
+static int launch_mlp_pad(const MlpArgs& a, hipStream_t s) {
+    const int n = NT3 == 0 ? 2 : 3;
+    bool hidden_gelu = true;
+    for (int l = 0; l + 1 < n; ++l) hidden_gelu = hidden_gelu && a.act[l] == HGNN_ACT_GELU;
+    const int out = a.act[n - 1];
+    if (hidden_gelu && out == HGNN_ACT_TANH)
+        return launch_mlp_act<NT1, NT2, NT3, MINW, HGNN_ACT_GELU, HGNN_ACT_TANH, false, 4, false, true>(a, s);
+    if (hidden_gelu && out == HGNN_ACT_GELU)
+        return launch_mlp_act<NT1, NT2, NT3, MINW, HGNN_ACT_GELU, HGNN_ACT_GELU, false, 4, false, true>(a, s);
+    return launch_mlp_act<NT1, NT2, NT3, MINW, -1, -1, false, 4, false, true>(a, s);
+}
+
+template <int NTH, int MINW>
+static int launch_head_pad(const MlpArgs& a, hipStream_t s) {
+    if (a.act[0] == HGNN_ACT_GELU && a.act[1] == HGNN_ACT_GELU)
+        return launch_mlp_act<NTH, NTH, 2, MINW, HGNN_ACT_GELU, HGNN_ACT_NONE, true, 4, true, true>(a, s);
+    return launch_mlp_act<NTH, NTH, 2, MINW, -1, HGNN_ACT_NONE, true, 4, true, true>(a, s);
+}
+
+// the grid width a hidden width h runs on: the smallest P of {32, 64, 128, 256} with 2P >= h (0: none)
+static int pad_grid(int h) {
+    if (h < 32 || h > 512 || h % 16 != 0) return 0;
+    for (int P = 32; P <= 256; P *= 2)
+        if (2 * P >= h) return P;
+    return 0;
 }
 
 // plain (no LayerNorm / activation) last layer of a 3-layer network = a head
@@ -604,5 +692,131 @@ extern "C" int hgnn_mlp_forward_f32(const hgnn_mlp_desc* d, float* out, hgnn_str
         }
     }
     set_error("hgnn_mlp_forward_f32: no instantiation");
+    return HGNN_ERR_UNSUPPORTED;
+}
+
+extern "C" int hgnn_mlp_supported_f32_padded(const hgnn_mlp_desc* d) {
+    if (d == nullptr) return 0;
+    if (d->n_seg < 1 || d->n_seg > 3 || d->n_layers < 2 || d->n_layers > 3) return 0;
+    int k = 0;
+    bool aligned16 = true;
+    for (int s = 0; s < d->n_seg; ++s) {
+        if (d->seg_width[s] <= 0) return 0;
+        aligned16 = aligned16 && d->seg_width[s] % 16 == 0;
+        k += d->seg_width[s];
+    }
+    if (k != d->width[0]) return 0;
+    if (!aligned16) {  // small-K mode: one zero-padded 16-column chunk
+        if (k > 16 || d->w0_cols != 16) return 0;
+    } else if (d->w0_cols != 0 && d->w0_cols != k) {
+        return 0;
+    }
+    const int n = d->n_layers;
+    for (int l = 0; l < n; ++l)
+        if (d->W[l] == nullptr || d->b[l] == nullptr) return 0;
+    if (d->n_pre < 0 || d->n_pre > 2) return 0;
+    for (int s = 0; s < d->n_pre; ++s)
+        if (d->pre_table[s] == nullptr || d->pre_index[s] == nullptr) return 0;
+    const int h = d->width[1];
+    const int o = d->width[n];
+    if (n == 3 && d->width[2] != h) return 0;
+    const int P = pad_grid(h);
+    if (P == 0) return 0;
+    if (d->ln_w[0] == nullptr || d->ln_b[0] == nullptr || d->ln_w[1] == nullptr || d->ln_b[1] == nullptr) return 0;
+    if (is_head(d)) {
+        // K -> H -> H -> w (w <= 32): hidden layers stored 2P wide, the plain last layer as 32 rows of 2P columns
+        if (o < 1 || o > 32 || d->w_last_rows != 32 || d->act[2] != HGNN_ACT_NONE) return 0;
+        if (d->skip != nullptr || d->save_pre[2] != nullptr) return 0;
+        return 1;
+    }
+    if (n == 3 && (d->ln_w[2] == nullptr || d->ln_b[2] == nullptr)) return 0;
+    // K -> h (-> h) -> o: hidden layers stored 2P wide, the last layer as P rows
+    if (o < 4 || (o & 3) != 0 || 2 * o > h || d->w_last_rows != P) return 0;
+    return 1;
+}
+
+extern "C" int hgnn_mlp_forward_f32_padded(const hgnn_mlp_desc* d, float* out, hgnn_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    HGNN_REQUIRE(d != nullptr && out != nullptr, "hgnn_mlp_forward_f32_padded: NULL argument");
+    if (!hgnn_mlp_supported_f32_padded(d)) {
+        set_error("hgnn_mlp_forward_f32_padded: unsupported shape (see hgnn_mlp_supported_f32_padded in "
+                  "include/hgnn_hip.h: K -> h (-> h) -> o with LayerNorm everywhere, h a multiple of 16 in [32, 512], "
+                  "o a multiple of 4 in [4, h / 2], parameters zero padded to the next grid width; or a "
+                  "K -> H -> H -> w head)");
+        return HGNN_ERR_UNSUPPORTED;
+    }
+    if (d->M == 0) return HGNN_OK;
+    HGNN_REQUIRE(d->M > 0 && d->M < ((int64_t)1 << 31) * 64, "hgnn_mlp_forward_f32_padded: bad M");
+    const int n = d->n_layers;
+    MlpArgs a;
+    for (int s = 0; s < 3; ++s) {
+        a.seg_table[s] = s < d->n_seg ? d->seg_table[s] : nullptr;
+        a.seg_index[s] = s < d->n_seg ? d->seg_index[s] : nullptr;
+        a.seg_width[s] = s < d->n_seg ? d->seg_width[s] : 0;
+        if (s < d->n_seg) {
+            HGNN_REQUIRE(a.seg_table[s] != nullptr && (uintptr_t)a.seg_table[s] % 16 == 0,
+                         "hgnn_mlp_forward_f32_padded: segment table %d is NULL or not 16-byte aligned", s);
+        }
+    }
+    a.n_seg = d->n_seg;
+    a.K1_real = d->width[0];
+    a.K1 = d->w0_cols != 0 ? d->w0_cols : d->width[0];
+    a.n_out_real = d->width[n];
+    for (int l = 0; l < 3; ++l) {
+        const bool on = l < n;
+        a.W[l] = on ? d->W[l] : nullptr;
+        a.b[l] = on ? d->b[l] : nullptr;
+        a.lnw[l] = on ? d->ln_w[l] : nullptr;
+        a.lnb[l] = on ? d->ln_b[l] : nullptr;
+        a.act[l] = on ? d->act[l] : 0;
+        a.real[l] = on ? d->width[l + 1] : 0;
+        if (on) {
+            HGNN_REQUIRE((uintptr_t)a.W[l] % 16 == 0 && (uintptr_t)a.b[l] % 16 == 0 &&
+                             (uintptr_t)a.lnw[l] % 16 == 0 && (uintptr_t)a.lnb[l] % 16 == 0,
+                         "hgnn_mlp_forward_f32_padded: layer %d parameters must be 16-byte aligned", l);
+        }
+        if (on && a.lnw[l] == nullptr) a.lnw[l] = a.lnb[l] = a.b[l];  // never dereferenced (plain layer)
+        a.save_pre[l] = on ? d->save_pre[l] : nullptr;
+        HGNN_REQUIRE((uintptr_t)a.save_pre[l] % 16 == 0,
+                     "hgnn_mlp_forward_f32_padded: save_pre[%d] must be 16-byte aligned", l);
+    }
+    a.ablate = g_opt_mlp_ablate;
+    a.eps = d->ln_eps;
+    a.skip = d->skip;
+    a.out = out;
+    a.n_pre = d->n_pre;
+    for (int s = 0; s < 2; ++s) {
+        a.pre_table[s] = s < d->n_pre ? d->pre_table[s] : nullptr;
+        a.pre_index[s] = s < d->n_pre ? d->pre_index[s] : nullptr;
+        HGNN_REQUIRE((uintptr_t)a.pre_table[s] % 16 == 0,
+                     "hgnn_mlp_forward_f32_padded: pre_table[%d] must be 16-byte aligned", s);
+    }
+    a.M = d->M;
+    HGNN_REQUIRE((uintptr_t)out % 16 == 0 && (uintptr_t)a.skip % 16 == 0,
+                 "hgnn_mlp_forward_f32_padded: out/skip must be 16-byte aligned");
+    const int P = pad_grid(d->width[1]);
+    if (is_head(d)) {
+        switch (P) {
+            case 32: return launch_head_pad<4, 2>(a, stream);
+            case 64: return launch_head_pad<8, 2>(a, stream);
+            case 128: return launch_head_pad<16, 2>(a, stream);
+            case 256: return launch_head_pad<32, 1>(a, stream);
+        }
+    } else if (n == 2) {
+        switch (P) {
+            case 32: return launch_mlp_pad<4, 2, 0, 2>(a, stream);
+            case 64: return launch_mlp_pad<8, 4, 0, 2>(a, stream);
+            case 128: return launch_mlp_pad<16, 8, 0, 2>(a, stream);
+            case 256: return launch_mlp_pad<32, 16, 0, 2>(a, stream);
+        }
+    } else {
+        switch (P) {
+            case 32: return launch_mlp_pad<4, 4, 2, 2>(a, stream);
+            case 64: return launch_mlp_pad<8, 8, 4, 2>(a, stream);
+            case 128: return launch_mlp_pad<16, 16, 8, 2>(a, stream);
+            case 256: return launch_mlp_pad<32, 32, 16, 1>(a, stream);
+        }
+    }
+    set_error("hgnn_mlp_forward_f32_padded: no instantiation");
     return HGNN_ERR_UNSUPPORTED;
 }

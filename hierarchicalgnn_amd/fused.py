@@ -1,7 +1,8 @@
 """Fused gather -> concat -> [Linear -> LayerNorm -> act] x {2,3} -> (+skip) on MFMA:
 ``hgnn_mlp_forward_f32`` (csrc/mlp_fused.hip, fp32 rows) and ``hgnn_mlp_forward_bf16``
 (csrc/mlp_fused_bf16.hip, bf16 rows).  Covers the cell networks, the encoders (small-K mode)
-and the width-1 classifier heads.
+and the width-1 classifier heads; fp32 rows at every hidden width that is a multiple of 16 up to 512
+(``hgnn_mlp_forward_f32_padded``: zero-padded parameters on the next instantiation of the template grid).
 
 ``_route`` decides per call (``supported`` asks it); when it says no, ``concat_mlp`` evaluates the same
 Sequential with HIP row gathers + library GEMMs (still on the GPU).  The fused kernel is
@@ -35,7 +36,7 @@ _enabled = True
 # segment-reduced dz it is faster (L=256, M=2M cell step: 58 vs 122 ms checkpointed, 45 vs 92 ms
 # without checkpointing) and is the default when autograd records.
 _train_enabled = True
-stats = {"fused_calls": 0, "fused_train_calls": 0}
+stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0}
 
 # Dispatch switches.  The module-level ``_name`` variables below are the PROCESS DEFAULTS (what the ``set_*`` functions
 # and the HGNN_* environment variables change).  ``options(...)`` overrides any of them for the current context only --
@@ -146,9 +147,34 @@ def _pad_rows(t: torch.Tensor, rows: int) -> torch.Tensor:
     return out
 
 
+def _pad_grid(h: int) -> int:
+    """the grid width P whose instantiation a hidden width ``h`` runs on (hgnn_mlp_forward_f32_padded): the smallest of
+    32, 64, 128, 256 with 2P >= h; 0 = none"""
+    if h % 16 or not 32 <= h <= 512:
+        return 0
+    return next(P for P in (32, 64, 128, 256) if 2 * P >= h)
+
+
+def _padded_param(param, rows: int, cols: Optional[int] = None, kept_cols=None, k_cols: Optional[int] = None):
+    """zero-padded copy of a Linear / LayerNorm parameter for hgnn_mlp_forward_f32_padded, cached per parameter object
+    and version (``_cached``): a weight [out, in] -> [rows, cols] (first layer: only the column blocks ``kept_cols``,
+    then ``k_cols`` = 16 columns in small-K mode), a vector [out] -> [rows]"""
+    def make():
+        t = param.detach()
+        if t.dim() == 1:
+            return _pad_rows(t, rows)
+        if kept_cols is not None:
+            t = torch.cat([t[:, c0:c1] for c0, c1 in kept_cols], dim=1)
+        width = cols if cols is not None else (k_cols if k_cols is not None else int(t.shape[1]))
+        out = torch.zeros((rows, width), dtype=t.dtype, device=t.device)
+        out[:t.shape[0], :t.shape[1]] = t
+        return out
+    return _cached(param, ("f32_padded", rows, cols, kept_cols, k_cols), make)
+
+
 def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = False, dry: bool = False, layers=None):
-    """(descriptor, keep-alive list, M, n_out) for ``hgnn_mlp_forward_<entry>`` (``entry`` in f32, f32_split3, bf16,
-    bf16_split), or None.  ``layers``: ``_parse(net)`` when the caller has it (then ``net`` is not read).
+    """(descriptor, keep-alive list, M, n_out) for ``hgnn_mlp_forward_<entry>`` (``entry`` in f32, f32_padded,
+    f32_split3, bf16, bf16_split), or None.  ``layers``: ``_parse(net)`` when the caller has it (then ``net`` is not read).
 
     One walk for every kernel: the segments (one row count M, int32 gather indices, pre-projected segments
     ``hgnn_mlp_desc.n_pre`` vs the ones kept in the kernel's K loop), the layers (chained widths, one LayerNorm eps)
@@ -178,6 +204,10 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
             return None
     lin0 = layers[0][0]
     if lin0.in_features != sum(int(t.shape[1]) for t, _ in segments) or not lin0.weight.is_cuda:
+        return None
+    padded = entry == "f32_padded"
+    P_grid = _pad_grid(int(lin0.out_features)) if padded else 0
+    if padded and (P_grid == 0 or len(layers) < 2):
         return None
     if bf16:
         pre = _opt("preproject_bf16")
@@ -222,6 +252,8 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
                         # the kernel reads P in its row dtype; bf16: bf16 operands, fp32 accumulation, one rounding --
                         # the arithmetic the kernel's own MFMAs would do
                         P = torch.matmul(t.detach(), (W_s.to(torch.bfloat16) if bf16 else W_s).t())   # [rows, H]
+                    if padded and int(P.shape[1]) < 2 * P_grid:
+                        P = torch.nn.functional.pad(P, (0, 2 * P_grid - int(P.shape[1])))   # the padded W[0] rows: zeros
                 keep.append(P)
             d.pre_table[n_pre] = P.data_ptr()
             d.pre_index[n_pre] = i32.data_ptr() if i32.numel() else None
@@ -267,17 +299,34 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
             if any(not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous()
                    for p in (W, b) + ((lnw, lnb) if ln is not None else ())):
                 return None
-            if entry == "f32_split3" and not dry:
+            small_k = l == 0 and any(int(t.shape[1]) % 16 for t, _ in segments)
+            if small_k and K > 16:
+                return None
+            if padded:
+                # widths between the grid's: every parameter zero padded to the instantiation of P_grid (layout:
+                # hgnn_mlp_supported_f32_padded in include/hgnn_hip.h); cached copies, the kernel's statistics, dumps
+                # and stores use the real widths in d.width
+                rows = 32 if ln is None else (P_grid if l == n - 1 else 2 * P_grid)
+                if small_k:
+                    d.w0_cols = 16
+                if l == n - 1:
+                    d.w_last_rows = rows
+                if not dry:
+                    W = _padded_param(lin.weight, rows, 2 * P_grid if l > 0 else None, cols, 16 if small_k else None)
+                    b = _padded_param(lin.bias, rows)
+                    if ln is not None:
+                        lnw, lnb = _padded_param(ln.weight, rows), _padded_param(ln.bias, rows)
+            elif entry == "f32_split3" and not dry:
                 W = _split3_weight(lin.weight, cols, l == 0)
             elif cols and not dry:
                 W = torch.cat([W[:, c0:c1] for c0, c1 in cols], dim=1).contiguous()
-            if l == 0 and any(int(t.shape[1]) % 16 for t, _ in segments):
-                if K > 16:
-                    return None
+            if small_k and not padded:
                 # small-K mode (encoders, K = 3 / 6): one zero-padded 16-column chunk
                 W = torch.nn.functional.pad(W, (0, 16 - K)).contiguous()
                 d.w0_cols = 16
-            if l == n - 1 and ln is None:
+            if padded:
+                pass                                      # stored rows and w_last_rows are set above
+            elif l == n - 1 and ln is None:
                 if o_l > 32:
                     return None
                 # head (width-1 classifiers, emb_dim-wide embedding head): the plain last layer is stored
@@ -573,7 +622,7 @@ class _Route(NamedTuple):
     """what ``_run`` launches for one call (``_route``)"""
     net: nn.Module
     layers: list               # _parse(net)
-    entry: str                 # each launch calls hgnn_mlp_forward_<entry>: f32, f32_split3, bf16 or bf16_split
+    entry: str                 # each launch calls hgnn_mlp_forward_<entry>: f32, f32_split3, bf16, bf16_split or f32_padded
     split_proj: bool = False   # f32_split3: pre-projections in the kernel's arithmetic (``_descriptor``)
     chain: bool = False        # one launch per LayerNorm'ed layer (+ a trailing plain Linear)
     head: bool = False         # score head: the plain last Linear runs outside the kernel, on the hidden rows
@@ -586,13 +635,15 @@ def _route(net, segments, skip, *, train: bool, allow_chain: bool = True) -> Opt
 
     ``train=False``: a forward autograd does not record (no grad mode, or nothing requires grad).  fp32 rows: the whole
     network in one launch (hgnn_mlp_forward_f32), else -- ``allow_chain`` -- one launch per layer (latent 512; a caller
-    with a cheaper alternative, the bf16 tail of the encoders, passes False).  Among these, with the split-bf16
+    with a cheaper alternative, the bf16 tail of the encoders, passes False), else -- widths between the kernel's
+    template grid -- one launch on zero-padded parameters (hgnn_mlp_forward_f32_padded, exact fp32 only).  Among these, with the split-bf16
     arithmetic on (``_split3``): score heads K -> H -> H -> w (H in 256, 512) run their hidden layers on
     hgnn_mlp_forward_f32_split3 and the last Linear as a product over the hidden rows; networks of its shapes run whole
     on it.  bf16 rows: the feature-split kernel where it wants the shape (``bf16_split``) else the plain bf16 kernel,
     else the single-layer chain on the split kernel.
     ``train=True``: autograd records.  fp32: the kernel's shapes with LayerNorm on every layer (f32_split3 when
-    ``_split3(net, train=True)``), and score heads (dumps of their hidden layers); bf16: the feature-split kernel."""
+    ``_split3(net, train=True)``), and score heads (dumps of their hidden layers); the padded widths with LayerNorm on
+    every layer (their heads train on the library path); bf16: the feature-split kernel."""
     if train:
         if not _opt("train_enabled") or not torch.is_grad_enabled():
             return None
@@ -655,6 +706,10 @@ def _route(net, segments, skip, *, train: bool, allow_chain: bool = True) -> Opt
         # kernel-side zero padding of W[0]) do -- their backward uses the unpadded parameters; score heads (plain last
         # layer stored as 32 rows) dump their two hidden layers
         head = len(layers) == 3 and plain_last
+        if not ok and not plain_last and dry("f32_padded")[1]:
+            # widths between the grid's: the same kernel on zero-padded parameters, dumps at the real widths; the
+            # backward takes any width (ATen rows where the HIP row kernels have no instantiation)
+            return _Route(net, layers, "f32_padded", train=True)
         if not ok or (int(desc[0].w_last_rows) != 0 and not head):
             return None
         if head and (skip is not None or any(lin.out_features not in (64, 128, 256, 512) for lin, _, _ in layers[:2])):
@@ -669,7 +724,9 @@ def _route(net, segments, skip, *, train: bool, allow_chain: bool = True) -> Opt
     desc, ok = dry("f32")
     chain = not ok and allow_chain and chain_ok()
     if not ok and not chain:
-        return None
+        # widths between the grid's (latent 48, 96, 160, 192, hidden_ratio 3, ...): zero-padded parameters on the next
+        # grid instantiation of the exact fp32 kernel
+        return _Route(net, layers, "f32_padded") if dry("f32_padded")[1] else None
     if _split3(net) and skip is None and len(layers) == 3 and plain_last \
             and layers[0][0].out_features in (256, 512) and layers[1][0].out_features == layers[0][0].out_features \
             and all(t.dtype == torch.float32 and int(t.shape[1]) % 128 == 0 for t, _ in segments):
@@ -710,6 +767,8 @@ def _forward(entry, d, out, dev):
     _lib.check(getattr(_lib.load(), name)(ctypes.byref(d), _lib.ptr(out), _lib.current_stream(dev)), name)
     if entry == "f32_split3":
         stats["split3_calls"] = stats.get("split3_calls", 0) + 1
+    elif entry == "f32_padded":
+        stats["padded_calls"] += 1
 
 
 def _launch(layers, segments, skip, entry, split_proj=False, out=None):

@@ -391,6 +391,28 @@ int hgnn_mlp_supported(const hgnn_mlp_desc* d);
  * registers.  Negative gather indices read row 0 (callers validate indices at plan build). */
 int hgnn_mlp_forward_f32(const hgnn_mlp_desc* d, float* out, hgnn_stream_t stream);
 
+/* Widths BETWEEN the grid's (a latent / hidden_ratio sweep: latent 48, 96, 160, 192, hidden = 3 x latent, ...): the
+ * same exact-fp32 kernel on the instantiation of the next grid width, with zero-padded parameters.
+ *   cell networks / encoders: K -> h (-> h) -> o, LayerNorm on every layer, h % 16 == 0, 32 <= h <= 512,
+ *       o % 4 == 0, 4 <= o <= h / 2; segments as for hgnn_mlp_supported (multiples of 16, or small-K mode); skip,
+ *       n_pre and save_pre allowed;
+ *   heads: K -> H -> H -> w, plain last layer of 1 <= w <= 32 outputs, H % 16 == 0, 32 <= H <= 512, no skip,
+ *       save_pre[0..1] allowed.
+ * Let P = the smallest of {32, 64, 128, 256} with 2P >= h (heads: >= H).  width[] carries the REAL widths; the storage
+ * the kernel reads follows from them:
+ *   W[0]            [2P, K]  rows h .. 2P-1 zero (K = width[0], or w0_cols = 16 columns in small-K mode);
+ *   W[1] (3 layers) [2P, 2P] rows and columns h .. 2P-1 zero;
+ *   last W          [P, 2P]  rows o .. P-1 and columns h .. 2P-1 zero (heads: [32, 2P], rows w .. 31 zero);
+ *   b, ln_w, ln_b of every layer: as many entries as the layer's W has rows, the padded ones ZERO (ln_w too: a padded
+ *       feature must come out as 0, it is the next layer's input);
+ *   w_last_rows = P (heads: 32), checked;
+ *   pre_table[s]    [rows, 2P] = table W_s^T with the padded W[0]: columns h .. 2P-1 zero.
+ * LayerNorm statistics run over the real features only (padded ones are masked out of the centred pass).  Rows in
+ * HBM have their real widths: skip and out are [M, o], save_pre[l] is [M, width[l+1]].
+ * The check accepts grid shapes too (no padding); hgnn_mlp_supported / hgnn_mlp_forward_f32 do not read this layout. */
+int hgnn_mlp_supported_f32_padded(const hgnn_mlp_desc* d);
+int hgnn_mlp_forward_f32_padded(const hgnn_mlp_desc* d, float* out, hgnn_stream_t stream);
+
 /* bf16 variant (BASELINE config 4 dtype) on v_mfma_f32_16x16x32_bf16.  Same descriptor, read as:
  * seg_table / skip / out = bf16 rows; W[l] = bf16 [out][in] row-major, and for l >= 1 with its
  * COLUMNS stored in MFMA k-slot order: column 32c + 8g + j holds input feature
