@@ -13,6 +13,7 @@ Drop-in surface (same names / signatures as the reference):
     weighted_bce_loss(...), ec_training_loss(...), ec_shared_evaluation(...)   <- EdgeClassifierBase.training_step / shared_evaluation
     hdbscan(points, min_cluster_size), embedding_track_candidates(...)   <- cuml.cluster.HDBSCAN (embedding validation)
     FusedAdamW(params, lr, ...), configure_optimizers(...), optimizer_step(...)   <- Trainer(gradient_clip_val) + AdamW(amsgrad) of every base
+    knn_edges(idx, n_pts, sym), attention_weights(src, dst, graph, bn, weighting, ...)   <- DynamicGraphConstruction's edge list and weights
 
 Everything on the hot path runs in hand-written HIP kernels loaded from
 libhgnn_hip.so through the C ABI of include/hgnn_hip.h; there is no CPU or
@@ -35,5 +36,7 @@ from .assignment import (max_weight_matching, bipartite_loss, bc_embedding_loss,
 from .edge_classifier import (weighted_bce_loss, weighted_bce_check, ec_training_loss,  # noqa: F401
                               ec_shared_evaluation)
 from .optim import FusedAdamW, configure_optimizers, optimizer_step  # noqa: F401
+from .ops import knn_edges  # noqa: F401
+from .graph_construction import attention_weights  # noqa: F401
 
 __version__ = "0.1.0"

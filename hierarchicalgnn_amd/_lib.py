@@ -53,6 +53,14 @@ OPT_AMSGRAD, OPT_CLIP, OPT_ZERO_GRADS, OPT_WRITE_GRADS, OPT_SCALAR = 1, 2, 4, 8,
 OPT_ST_NONFINITE = 1
 OPT_NORM, OPT_COEF, OPT_SUMSQ = range(3)
 OPT_STATE = 4
+# HGNN_GC_* / HGNN_GA_*: hgnn_knn_edges' status bit; hgnn_graph_attention_*'s limits, function codes, flag bits and
+# device state vector
+GC_ST_BAD_ID = 1
+GA_MAX_DIM = 16
+GA_FN_SIGMOID, GA_FN_EXP = 0, 1
+GA_TRAINING, GA_NORM = 1, 2
+GA_MEAN, GA_VAR, GA_RSTD, GA_SUMF, GA_E, GA_DBETA, GA_DGAMMA, GA_SGF = range(8)
+GA_STATE = 8
 
 class HgnnPlan(Structure):
     """mirror of ``struct hgnn_plan``"""
@@ -199,6 +207,16 @@ _SIGNATURES = {
                                      c_void_p, c_size_t, c_void_p]),
     "hgnn_optim_adamw_step": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                       c_int32, c_void_p, c_void_p]),
+    "hgnn_knn_edges_workspace_bytes": (c_int, [c_int64, c_int32, c_int64, c_int32, POINTER(c_size_t)]),
+    "hgnn_knn_edges": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
+    "hgnn_graph_attention_workspace_bytes": (c_int, [c_int64, c_int32, POINTER(c_size_t)]),
+    "hgnn_graph_attention_forward": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int64,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double,
+                                             c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_size_t, c_void_p]),
+    "hgnn_graph_attention_backward": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -569,6 +569,48 @@ def knn_radius_stats():
     return int(v), int(s)
 
 
+gc_stats = {"host_reads": 0}   # graph_construction.stats: the host reads of the device-side graph route
+
+
+def knn_edges(idx: torch.Tensor, n_pts: int, sym: bool = False) -> torch.Tensor:
+    """The edge list of a kNN result ``idx`` int64 [nq, K] (``knn_radius``'s: ids in [0, n_pts), -1 = empty slot) as
+    ``DynamicGraphConstruction.build_graph`` forms it: the pairs (row, id) of the valid slots in row-major order, or
+    with ``sym`` the union of both directions without duplicates in ascending (src, dst) order (``symmetrize`` with
+    n = max(nq, n_pts)).  Built on the device (csrc/graphcon.hip) with ONE host read -- the edge count and the status
+    word together, counted in ``graph_construction.stats["host_reads"]``.  Returns a contiguous int64 [2, B] tensor.
+    ValueError if an id is >= n_pts or < -1."""
+    if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[1] < 1:
+        raise ValueError("knn_edges: idx must be an int64 [nq, K >= 1] tensor")
+    nq, K, n_pts = int(idx.shape[0]), int(idx.shape[1]), int(n_pts)
+    if n_pts < 0 or max(nq, n_pts) > 2 ** 31:
+        raise ValueError(f"knn_edges: n = max(nq, n_pts) = {max(nq, n_pts)} must be in [0, 2^31]")
+    if nq * K >= 2 ** 30:
+        raise ValueError(f"knn_edges: nq * K = {nq * K} must stay below 2^30")
+    if not idx.is_cuda:
+        raise RuntimeError("knn_edges needs a HIP device tensor: hierarchicalgnn_amd has no CPU path")
+    dev = idx.device
+    cap = (2 if sym else 1) * nq * K
+    if cap == 0:
+        return torch.empty((2, 0), dtype=torch.int64, device=dev)
+    idx_c = idx.detach().contiguous()
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(lib.hgnn_knn_edges_workspace_bytes(nq, K, n_pts, int(bool(sym)), ctypes.byref(nbytes)),
+               "hgnn_knn_edges_workspace_bytes")
+    ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=dev)
+    edges = torch.empty((2, cap), dtype=torch.int64, device=dev)
+    info = torch.empty(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.hgnn_knn_edges(_lib.ptr(idx_c), nq, K, n_pts, int(bool(sym)), _lib.ptr(edges), cap,
+                                      _lib.ptr(info), _lib.ptr(ws), int(nbytes.value), _lib.current_stream(dev)),
+                   "hgnn_knn_edges")
+    gc_stats["host_reads"] += 1
+    count, status = info.tolist()
+    if status & _lib.GC_ST_BAD_ID:
+        raise ValueError(f"knn_edges: a neighbour id is >= n_pts = {n_pts} or < -1")
+    return edges[:, :count].contiguous()
+
+
 def _wgrad_operand(t: torch.Tensor) -> torch.Tensor:
     """an operand of the weight-gradient kernels as they can read it: 16-byte pieces of row-major rows.  A view with a
     column stride, with a row stride that is no multiple of 16 bytes, or whose first element is not 16-byte aligned (a

@@ -821,6 +821,77 @@ int hgnn_optim_adamw_step(const hgnn_opt_entry* host_table, const hgnn_opt_entry
                           int64_t n_chunks, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
                           int64_t state_numel, int32_t flags, const double* state, hgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Graph construction after the neighbour search (reference Modules/gnn_utils.py:193-216, DynamicGraphConstruction):
+ * the edge list of a kNN result and the attention weights of its edges.  Added under ABI 26: additions only.
+ *
+ * hgnn_knn_edges: idx int64 [nq, K] as hgnn_knn_radius_* write it (ids in [0, n_pts), -1 = empty slot; the valid
+ *   slots need not be a prefix of their row).  edges int64 [2, cap], cap >= nq K (sym = 0) or 2 nq K (sym = 1): the
+ *   first B entries of both rows are written, B = count_and_status[0].
+ *     sym = 0: the pairs (row, idx[row, j]) of the valid slots in row-major order.
+ *     sym = 1: the union of (s, d) and (d, s) over the valid slots, duplicates removed, ascending in (s, d): the keys
+ *       (s << b | d), b = ceil(log2(max(nq, n_pts))), are sorted over their 2 b bits plus one for the empty-slot marker.
+ *   count_and_status device int64[2], cleared first: the edge count, and HGNN_GC_ST_BAD_ID when an id is >= n_pts or
+ *   < -1 (such a slot is skipped, never used as an address).  max(nq, n_pts) <= 2^31 and nq K < 2^30, else
+ *   HGNN_ERR_INVALID_ARG.  Runs on `stream` out of `workspace`: no allocation, no synchronisation, no read-back; the
+ *   only atomic is an integer OR into the status word.
+ * hgnn_knn_edges_workspace_bytes: device scratch of one call.  Computed on the host from the sizes, but it includes
+ *   rocprim's own scratch, whose size rocprim derives from the current device: the call needs the HIP runtime and a
+ *   device (as hgnn_graph_intersection_workspace_bytes and hgnn_assign_match_workspace_bytes do); the argument checks
+ *   come first.  hgnn_graph_attention_workspace_bytes is a pure host function.
+ *
+ * hgnn_graph_attention_forward: for E edges (a_e, b_e) = (graph[e], graph[E + e]) (int32 or int64 by index_dtype),
+ *   A float32 [Na, D], B float32 [Nb, D] (may be the same pointer), 1 <= D <= HGNN_GA_MAX_DIM:
+ *     x_e = <A[a_e], B[b_e]>                         bit-equal to hgnn_edge_dot_f32; 0 for an id out of range
+ *     z_e = bn_weight[0] (x_e - mu) rstd + bn_bias[0],  rstd = 1 / sqrt(var + eps)
+ *     f_e = sigmoid(z_e) (HGNN_GA_FN_SIGMOID) | exp(z_e) (HGNN_GA_FN_EXP)
+ *     w_e = f_e / (sum f / E) with HGNN_GA_NORM, else f_e
+ *   With HGNN_GA_TRAINING (E >= 2) mu and the biased var are the batch's, from float64 sums of x and x^2, and the
+ *   call then updates the running statistics as nn.BatchNorm1d does: num_batches_tracked += 1 (may be NULL),
+ *   running = (1 - m) running + m (mu | var E / (E - 1)), m = momentum, or 1 / num_batches_tracked for momentum < 0.
+ *   Without it mu and var are running_mean[0] and running_var[0] and nothing but the outputs is written.  Every sum
+ *   is float64 in a fixed order that depends on E alone: two calls give the same bits.  Outputs: x, logits (z),
+ *   weights float32 [E]; state device double[HGNN_GA_STATE] (indices below).  All BatchNorm arguments are device
+ *   pointers.  E = 0 without HGNN_GA_TRAINING does nothing.
+ * hgnn_graph_attention_backward: g_w float32 [E], g_logits float32 [E] or NULL; state as the forward wrote it (the
+ *   entries HGNN_GA_DBETA, HGNN_GA_DGAMMA, HGNN_GA_SGF are written here).  With m = sum f / E, xhat = (x - mu) rstd:
+ *     g_f = g_w / m - (sum g_w f) / (E m^2)   (g_w without HGNN_GA_NORM);   G = g_f phi'(z) + g_logits
+ *     g_bn = (dgamma, dbeta) = (sum G xhat, sum G)
+ *     g_x = gamma rstd (G - dbeta / E - xhat dgamma / E) with HGNN_GA_TRAINING, gamma rstd G without
+ *   g_x float32 [E] is d loss / d x; dA and dB follow from it by hgnn_segment_reduce_f32 over the plans of the two
+ *   graph rows, as for hgnn_edge_dot_f32.  No atomics.
+ * Both launch asynchronously, allocate nothing, never synchronise and read nothing back.
+ * hgnn_graph_attention_workspace_bytes: device scratch of one forward (backward = 0) or backward (1) call.
+ * ------------------------------------------------------------------------ */
+#define HGNN_GC_ST_BAD_ID 1
+#define HGNN_GA_MAX_DIM 16
+#define HGNN_GA_FN_SIGMOID 0
+#define HGNN_GA_FN_EXP 1
+#define HGNN_GA_TRAINING 1
+#define HGNN_GA_NORM 2
+#define HGNN_GA_MEAN 0
+#define HGNN_GA_VAR 1      /* biased */
+#define HGNN_GA_RSTD 2
+#define HGNN_GA_SUMF 3
+#define HGNN_GA_E 4
+#define HGNN_GA_DBETA 5
+#define HGNN_GA_DGAMMA 6
+#define HGNN_GA_SGF 7      /* sum g_w f */
+#define HGNN_GA_STATE 8
+int hgnn_knn_edges_workspace_bytes(int64_t nq, int32_t K, int64_t n_pts, int32_t sym, size_t* bytes);
+int hgnn_knn_edges(const int64_t* idx, int64_t nq, int32_t K, int64_t n_pts, int32_t sym, int64_t* edges, int64_t cap,
+                   int64_t* count_and_status, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
+int hgnn_graph_attention_workspace_bytes(int64_t E, int32_t backward, size_t* bytes);
+int hgnn_graph_attention_forward(const float* A, int64_t Na, const float* B, int64_t Nb, int32_t D, const void* graph,
+                                 int32_t index_dtype, int64_t E, const float* bn_weight, const float* bn_bias,
+                                 float* running_mean, float* running_var, int64_t* num_batches_tracked, double eps,
+                                 double momentum, int32_t flags, int32_t fn, float* x, float* logits, float* weights,
+                                 double* state, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
+int hgnn_graph_attention_backward(const float* x, int64_t E, const float* bn_weight, const float* bn_bias,
+                                  int32_t flags, int32_t fn, double* state, const float* g_w, const float* g_logits,
+                                  float* g_x, float* g_bn, void* workspace, size_t workspace_bytes,
+                                  hgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
