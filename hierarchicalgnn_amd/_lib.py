@@ -274,3 +274,58 @@ def ptr(t):
 def current_stream(device):
     import torch
     return c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def workspace(symbol: str, device, *args):
+    """(uint8 scratch tensor on ``device``, its size in bytes as the library counts it) for the size query ``symbol``
+    called with ``args`` and the byte count's address.  The tensor has at least one byte, so its pointer is never NULL."""
+    import torch
+    nb = c_size_t(0)
+    check(getattr(load(), symbol)(*args, byref(nb)), symbol)
+    return torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=device), int(nb.value)
+
+
+def index_dtype(t) -> int:
+    """HGNN_DT_* of an int64 or int32 index tensor"""
+    import torch
+    return DT_I64 if t.dtype == torch.int64 else DT_I32
+
+
+def pt_scalars(hparams):
+    """the host hparams vector of the pT-weighted losses with the five PH_* entries they share filled in"""
+    h = (c_double * PH_HPARAMS)()
+    h[PH_WEIGHT_MIN] = float(hparams["weight_min"])
+    h[PH_WEIGHT_LEAK] = float(hparams["weight_leak"])
+    h[PH_PTCUT] = float(hparams["ptcut"])
+    h[PH_PT_INTERVAL] = float(hparams["pt_interval"])
+    h[PH_LOG_WEIGHT_RATIO] = float(hparams["log_weight_ratio"])
+    return h
+
+
+class PendingStatus:
+    """The status words of the calls nobody has read yet: device -> int32[1], OR-ed on the device, so a call makes no
+    host read.  ``stats``: the owning module's counters; ``stats["host_reads"]`` counts one per device word read."""
+
+    def __init__(self, stats):
+        self.stats = stats
+        self.words = {}
+
+    def add(self, device, status):
+        word = self.words.get(device)
+        self.words[device] = status if word is None else word | status
+
+    def take(self, device=None) -> int:
+        """reads and clears the word of ``device`` (None: of every device); 0 if nothing is pending"""
+        import torch
+        if device is None:
+            devs = list(self.words)
+        else:
+            dev = torch.device(device)
+            devs = [dev if dev.index is not None else torch.device(dev.type, torch.cuda.current_device())]
+        out = 0
+        for dev in devs:
+            word = self.words.pop(dev, None)
+            if word is not None:
+                self.stats["host_reads"] += 1
+                out |= int(word.item())
+        return out

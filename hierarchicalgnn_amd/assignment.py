@@ -76,9 +76,7 @@ def max_weight_matching(row, col, score, n_rows: int, n_cols: int):
         raise ValueError("max_weight_matching: row, col and score need one entry per edge, on one device")
     dev = row.device
     lib = _lib.load()
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.hgnn_assign_match_workspace_bytes(B, P, C, ctypes.byref(nb)), "hgnn_assign_match_workspace_bytes")
-    ws = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev)
+    ws, nb = _lib.workspace("hgnn_assign_match_workspace_bytes", dev, B, P, C)
     col_match = torch.empty(P, dtype=torch.int64, device=dev)
     pair_row = torch.empty(B, dtype=torch.int64, device=dev)
     pair_col = torch.empty(B, dtype=torch.int64, device=dev)
@@ -87,7 +85,7 @@ def max_weight_matching(row, col, score, n_rows: int, n_cols: int):
     with torch.cuda.device(dev):
         _lib.check(lib.hgnn_assign_match(_lib.ptr(row), _lib.ptr(col), _lib.ptr(score), B, P, C, _lib.ptr(col_match),
                                          _lib.ptr(pair_row), _lib.ptr(pair_col), _lib.ptr(pair_w), info, _lib.ptr(ws),
-                                         int(nb.value), _lib.current_stream(dev)), "hgnn_assign_match")
+                                         nb, _lib.current_stream(dev)), "hgnn_assign_match")
     stats.update(host_reads=int(info[_lib.AM_HOST_READS]), phases=int(info[_lib.AM_PHASES]),
                  grid_rounds=int(info[_lib.AM_GRID_ROUNDS]), tail_rounds=int(info[_lib.AM_TAIL_ROUNDS]),
                  n_pairs=int(info[_lib.AM_N_PAIRS]))

@@ -483,10 +483,7 @@ extern "C" int hgnn_assign_match(const int64_t* row, const int64_t* col, const f
     AmWorkspace w;
     rc = am_layout(B, P, C, &w, stream);
     if (rc != HGNN_OK) return rc;
-    if (workspace == nullptr || workspace_bytes < w.total) {
-        set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, w.total);
-        return HGNN_ERR_WORKSPACE;
-    }
+    HGNN_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, w.total);
     char* ws = (char*)workspace;
     uint64_t *key = (uint64_t*)(ws + w.key), *key_s = (uint64_t*)(ws + w.key_s), *ukey = (uint64_t*)(ws + w.ukey);
     int32_t *pos = (int32_t*)(ws + w.pos), *pos_s = (int32_t*)(ws + w.pos_s);

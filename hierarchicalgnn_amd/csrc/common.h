@@ -28,6 +28,16 @@ void set_error(const char* fmt, ...);
         }                                                                             \
     } while (0)
 
+// the caller's workspace of `have` bytes at `ptr` must hold `need`
+#define HGNN_REQUIRE_WORKSPACE(what, ptr, have, need)                                 \
+    do {                                                                              \
+        if ((have) < (need) || (ptr) == nullptr) {                                    \
+            ::hgnn::set_error("%s: workspace too small (%zu < %zu)", what,            \
+                              (size_t)(have), (size_t)(need));                        \
+            return HGNN_ERR_WORKSPACE;                                                \
+        }                                                                             \
+    } while (0)
+
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -16,10 +16,11 @@
 //   z_e = gamma (x_e - mu) rstd + beta             mu, var: the batch's (training) or the running ones (eval)
 //   f_e = sigmoid(z_e) | exp(z_e),   w_e = f_e / (sum f / E) with norm, else f_e
 //   Every sum (sum x, sum x^2, sum f; backward: sum g_w f, sum G, sum G xhat) is float64: per thread in a fixed order,
-//   per workgroup through a fixed tree, one partial per workgroup, the partials added in index order (the k_wb
-//   pattern).  The grid depends on E alone, so the bits do too.  The elementwise part is float32 from the float64
+//   per workgroup through a fixed tree, one partial per workgroup, the partials added in index order
+//   (det_reduce.h).  The grid depends on E alone, so the bits do too.  The elementwise part is float32 from the float64
 //   scalars rounded once.  k_ga_stats also performs nn.BatchNorm1d's running-statistics update.
 #include "common.h"
+#include "det_reduce.h"
 #include "rows_common.h"
 #include <cmath>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -148,46 +149,8 @@ __global__ __launch_bounds__(kBlock) void k_gc_decode(const uint64_t* __restrict
 }
 
 // ------------------------------------------------------------------ k_ga
-constexpr int kGaMaxGrid = 2048;   // 256 CUs x 8 workgroups: one trip covers kGaMaxGrid * kBlock = 524288 edges
 constexpr int kGaMaxAcc = 2;
-constexpr size_t kGaWorkspaceBytes = (size_t)kGaMaxAcc * kGaMaxGrid * sizeof(double);
-
-unsigned ga_grid(int64_t E) {
-    const int64_t blocks = ceil_div(E, kBlock);
-    return (unsigned)(blocks < 1 ? 1 : (blocks > kGaMaxGrid ? kGaMaxGrid : blocks));
-}
-
-// fixed-shape sum of one double per thread over the workgroup: xor tree inside the wave, then the waves in order
-__device__ __forceinline__ double ga_block_sum(double v, double* lds) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    const int wave = threadIdx.x / kWave;
-    __syncthreads();
-    if (threadIdx.x % kWave == 0) lds[wave] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < kWavesPerBlock; ++w) t += lds[w];
-    return t;
-}
-
-template <int NACC>
-__device__ __forceinline__ void ga_write_partials(const double* acc, double* lds, double* __restrict__ partials) {
-    for (int k = 0; k < NACC; ++k) {
-        const double s = ga_block_sum(acc[k], lds);
-        if (threadIdx.x == 0) partials[(int64_t)k * gridDim.x + blockIdx.x] = s;
-    }
-}
-
-// thread t adds partials t, t + 256, .. in that order, then the fixed tree (one workgroup)
-template <int NACC>
-__device__ __forceinline__ void ga_total(const double* __restrict__ partials, int n_partials, double* lds,
-                                         double* tot) {
-    for (int k = 0; k < NACC; ++k) {
-        double v = 0.0;
-        for (int j = threadIdx.x; j < n_partials; j += kBlock) v += partials[(int64_t)k * n_partials + j];
-        tot[k] = ga_block_sum(v, lds);
-    }
-}
+constexpr size_t kGaWorkspaceBytes = (size_t)kGaMaxAcc * kDetMaxGrid * sizeof(double);
 
 // <A[a], B[b]> as hgnn_edge_dot_f32 forms it.  VEC (D % 4 == 0, 16-byte aligned tables; k_edge_dot with 4 lanes per
 // row): lane c holds q_c = the 4-term expression of its 16-byte column, the row is (q0 + q1) + (q2 + q3) with 0 for
@@ -240,7 +203,7 @@ __global__ __launch_bounds__(kBlock) void k_ga_dot(const float* __restrict__ A, 
             acc[1] += (double)v * (double)v;
         }
     }
-    if (TRAIN) ga_write_partials<2>(acc, lds, partials);
+    if (TRAIN) write_partials<2>(acc, lds, partials);
 }
 
 // one workgroup.  Training: mu, biased var from the partials, then nn.BatchNorm1d's running update (unbiased
@@ -253,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void k_ga_stats(const double* __restrict__ 
                                                      double* __restrict__ state) {
     __shared__ double lds[kWavesPerBlock];
     double tot[2] = {0.0, 0.0};
-    if (train) ga_total<2>(partials, n_partials, lds, tot);
+    if (train) total_partials<2>(partials, n_partials, lds, tot);
     if (threadIdx.x != 0) return;
     double mu, var;
     if (train) {
@@ -300,7 +263,7 @@ __global__ __launch_bounds__(kBlock) void k_ga_apply(const float* __restrict__ x
         f[e] = v;
         acc[0] += (double)v;
     }
-    ga_write_partials<1>(acc, lds, partials);
+    write_partials<1>(acc, lds, partials);
 }
 
 // one workgroup: the partials of NACC sums -> state[slot .. slot + NACC)
@@ -309,7 +272,7 @@ __global__ __launch_bounds__(kBlock) void k_ga_finish(const double* __restrict__
                                                       double* __restrict__ state) {
     __shared__ double lds[kWavesPerBlock];
     double tot[NACC];
-    ga_total<NACC>(partials, n_partials, lds, tot);
+    total_partials<NACC>(partials, n_partials, lds, tot);
     if (threadIdx.x == 0)
         for (int k = 0; k < NACC; ++k) state[slot + k] = tot[k];
 }
@@ -336,7 +299,7 @@ __global__ __launch_bounds__(kBlock) void k_ga_bwd_gf(const float* __restrict__ 
         const float v = ga_phi<EXP>(g * ((x[e] - mu) * rstd) + b);
         acc[0] += (double)g_w[e] * (double)v;
     }
-    ga_write_partials<1>(acc, lds, partials);
+    write_partials<1>(acc, lds, partials);
 }
 
 // G_e = g_f phi'(z) + g_logits -> G (float32), partial sums of G and G xhat
@@ -365,7 +328,7 @@ __global__ __launch_bounds__(kBlock) void k_ga_bwd_G(const float* __restrict__ x
         acc[0] += (double)t;
         acc[1] += (double)t * (double)xh;
     }
-    ga_write_partials<2>(acc, lds, partials);
+    write_partials<2>(acc, lds, partials);
 }
 
 // g_x = gamma rstd (G - dbeta / E - xhat dgamma / E) in training, gamma rstd G in eval; thread 0 writes (dgamma, dbeta)
@@ -487,12 +450,9 @@ extern "C" int hgnn_graph_attention_forward(const float* A, int64_t Na, const fl
     HGNN_REQUIRE(A && B && graph && bn_weight && bn_bias && running_mean && running_var && x && logits && weights &&
                      state,
                  "%s: NULL pointer", who);
-    if (workspace == nullptr || workspace_bytes < kGaWorkspaceBytes) {
-        set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, kGaWorkspaceBytes);
-        return HGNN_ERR_WORKSPACE;
-    }
+    HGNN_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, kGaWorkspaceBytes);
     double* partials = (double*)workspace;
-    const unsigned grid = ga_grid(E);
+    const unsigned grid = det_grid(E);
     const bool vec = D % 4 == 0 && (uintptr_t)A % 16 == 0 && (uintptr_t)B % 16 == 0;
     auto dot = [&](auto it, auto vk, auto tr) {
         using IT = decltype(it);
@@ -531,12 +491,9 @@ extern "C" int hgnn_graph_attention_backward(const float* x, int64_t E, const fl
     const bool train = (flags & HGNN_GA_TRAINING) != 0, norm = (flags & HGNN_GA_NORM) != 0;
     HGNN_REQUIRE(E >= 1, "%s: need E >= 1", who);
     HGNN_REQUIRE(x && bn_weight && bn_bias && state && g_w && g_x && g_bn, "%s: NULL pointer", who);
-    if (workspace == nullptr || workspace_bytes < kGaWorkspaceBytes) {
-        set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, kGaWorkspaceBytes);
-        return HGNN_ERR_WORKSPACE;
-    }
+    HGNN_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, kGaWorkspaceBytes);
     double* partials = (double*)workspace;
-    const unsigned grid = ga_grid(E);
+    const unsigned grid = det_grid(E);
     const bool ex = fn == HGNN_GA_FN_EXP;
     if (norm) {
         if (ex) k_ga_bwd_gf<true><<<grid, kBlock, 0, stream>>>(x, E, bn_weight, bn_bias, state, g_w, partials);

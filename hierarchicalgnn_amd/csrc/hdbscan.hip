@@ -544,10 +544,7 @@ extern "C" int hgnn_hdbscan_f32(const float* points, int64_t N, int32_t D, int32
     HdbWorkspace w;
     rc = hdb_layout(N, &w);
     if (rc != HGNN_OK) return rc;
-    if (workspace == nullptr || workspace_bytes < w.total) {
-        set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, w.total);
-        return HGNN_ERR_WORKSPACE;
-    }
+    HGNN_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, w.total);
     const bool stage_sync = info != nullptr && info[HGNN_HDB_STAGE_SYNC] != 0;
     int64_t inf[HGNN_HDB_INFO] = {0};
     char* ws = (char*)workspace;

@@ -163,10 +163,7 @@ extern "C" int hgnn_graph_intersection(const int64_t* pred, int64_t e_pred, cons
     GiWorkspace w;
     rc = gi_layout(e_pred, e_truth, with_w, &w, stream);
     if (rc != HGNN_OK) return rc;
-    if (workspace == nullptr || workspace_bytes < w.total) {
-        set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, w.total);
-        return HGNN_ERR_WORKSPACE;
-    }
+    HGNN_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, w.total);
     char* ws = (char*)workspace;
     uint64_t *pkey = (uint64_t*)(ws + w.pkey), *pkey_s = (uint64_t*)(ws + w.pkey_s), *ukey = (uint64_t*)(ws + w.ukey);
     uint64_t *tkey = (uint64_t*)(ws + w.tkey), *tkey_s = (uint64_t*)(ws + w.tkey_s);

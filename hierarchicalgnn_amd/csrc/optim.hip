@@ -12,11 +12,12 @@
 // entry whose first_chunk <= c.  The map depends on the tensor sizes alone.  Inside a chunk, thread t owns the
 // elements 4 (t + 256 j) .. + 3 for j = 0 .. 3, whether they are loaded as one 16-byte word or one by one.
 //
-// k_opt_sumsq: sum of g^2 in float64 -- per thread in that fixed order, per workgroup through the fixed tree -- one
-// partial per workgroup; k_opt_norm_finish adds the partials in index order and writes state = {total_norm, coef,
-// sum}.  The grid is a function of the chunk count alone, so the bits are too.  k_opt_adamw: ONE pass, every array
-// read once and written once.  No atomics other than the status atomicOr.
+// k_opt_sumsq: sum of g^2 in float64 -- per thread in that fixed order, per workgroup through the fixed tree
+// (det_reduce.h's block_sum) -- one partial per workgroup; k_opt_norm_finish adds the partials in index order and
+// writes state = {total_norm, coef, sum}.  The grid is a function of the chunk count alone, so the bits are too.
+// k_opt_adamw: ONE pass, every array read once and written once.  No atomics other than the status atomicOr.
 #include "common.h"
+#include "det_reduce.h"
 #include <cmath>
 #include <type_traits>
 
@@ -27,7 +28,6 @@
 namespace hgnn {
 namespace {
 
-constexpr int kOptMaxGrid = 2048;                       // 256 CUs x 8 workgroups: cap, then stride over the chunks
 constexpr int kOptChunk = HGNN_OPT_CHUNK;
 constexpr int kOptGroups = kOptChunk / (4 * kBlock);    // 16-byte groups per thread and chunk
 static_assert(kOptGroups * 4 * kBlock == kOptChunk, "a chunk is a whole number of 16-byte groups per thread");
@@ -43,19 +43,6 @@ __device__ __forceinline__ int opt_find(const hgnn_opt_entry* __restrict__ table
         else hi = mid - 1;
     }
     return lo;
-}
-
-// fixed-shape sum of one double per thread over the workgroup: xor tree inside the wave, then the waves in order
-__device__ __forceinline__ double opt_block_sum(double v, double* lds) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    const int wave = threadIdx.x / kWave;
-    __syncthreads();
-    if (threadIdx.x % kWave == 0) lds[wave] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < kWavesPerBlock; ++w) t += lds[w];
-    return t;
 }
 
 // p and g come out of the table, so the compiler cannot know that they point to global memory: say so, or every
@@ -108,8 +95,8 @@ __global__ __launch_bounds__(kBlock) void k_opt_sumsq(const hgnn_opt_entry* __re
             }
         }
     }
-    const double s = opt_block_sum(acc, lds);
-    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+    const double s = block_sum(acc, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;          // det_reduce.h write_partials, one accumulator
 }
 
 // one workgroup: thread t adds partials t, t + 256, .. in that order, then the fixed tree.  coef in float32 as
@@ -120,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void k_opt_norm_finish(const double* __rest
     __shared__ double lds[kWavesPerBlock];
     double v = 0.0;
     for (int j = threadIdx.x; j < n_partials; j += kBlock) v += partials[j];
-    const double sum = opt_block_sum(v, lds);
+    const double sum = block_sum(v, lds);
     if (threadIdx.x == 0) {
         const double norm = sqrt(sum);
         const float c = max_norm / ((float)norm + 1e-6f);
@@ -234,9 +221,10 @@ __global__ __launch_bounds__(kBlock) void k_opt_adamw(const hgnn_opt_entry* __re
     }
 }
 
-unsigned opt_grid(int64_t n_chunks) { return (unsigned)(n_chunks > kOptMaxGrid ? kOptMaxGrid : n_chunks); }
+// one workgroup per chunk up to the cap, then a stride over the chunks; 0 chunks launch nothing
+unsigned opt_grid(int64_t n_chunks) { return (unsigned)(n_chunks > kDetMaxGrid ? kDetMaxGrid : n_chunks); }
 
-constexpr size_t kOptWorkspaceBytes = (size_t)kOptMaxGrid * sizeof(double);   // the partials
+constexpr size_t kOptWorkspaceBytes = (size_t)kDetMaxGrid * sizeof(double);   // the partials
 
 // the HOST copy of the table is what is checked: every kernel access lies inside [p, p + numel), [g, g + numel) and
 // [offset, offset + numel) of the state buffers when it passes
@@ -286,10 +274,7 @@ extern "C" int hgnn_optim_grad_norm(const hgnn_opt_entry* host_table, const hgnn
     if (rc != HGNN_OK) return rc;
     HGNN_REQUIRE(state != nullptr && status != nullptr, "hgnn_optim_grad_norm: NULL pointer");
     HGNN_REQUIRE((flags & ~HGNN_OPT_SCALAR) == 0, "hgnn_optim_grad_norm: only HGNN_OPT_SCALAR may be set in flags");
-    if (workspace_bytes < kOptWorkspaceBytes || workspace == nullptr) {
-        set_error("hgnn_optim_grad_norm: workspace too small (%zu < %zu)", workspace_bytes, kOptWorkspaceBytes);
-        return HGNN_ERR_WORKSPACE;
-    }
+    HGNN_REQUIRE_WORKSPACE("hgnn_optim_grad_norm", workspace, workspace_bytes, kOptWorkspaceBytes);
     double* partials = (double*)workspace;
     const unsigned grid = opt_grid(n_chunks);
     if (grid > 0) {

@@ -7,34 +7,30 @@
 //
 // Forward: ONE pass over the pairs (k_ph_forward) that accumulates the four sums in float64 -- per thread in a fixed
 // order, per workgroup through a fixed tree -- and writes one partial per workgroup; k_ph_finish adds the partials in
-// index order.  The grid is a function of P alone, so the bits are too.  The class normalisation is applied to the
-// sums, not to every pair: no second pass and no [P] weight vector.
+// index order.  The grid is a function of P alone, so the bits are too: the tree, the grid and the id loader are
+// det_reduce.h's.  The class normalisation is applied to the sums, not to every pair: no second pass and no [P]
+// weight vector.
 // Backward: k_ph_coef writes one coefficient per pair; k_ph_grad walks the destination-sorted plan over cat(a, b)
 // (gather index cat(b, a): every pair sits in the list of both endpoints) and sums  grad[v] = sum c_i (E[v] - E[o])
 // over v's list in the plan's fixed order.  No floating-point atomics anywhere.
 // Streams per pair: the two ids and y.  E (N x D floats) and pt stay cache-resident; nothing of shape [P, D] exists.
 #include "common.h"
+#include "det_reduce.h"
+// ph_ptw(pt, params): pt_weighting in float32 with a NaN pt read as 0.  It lives in a header of its own because
+// k_wb_* (wbce.hip, the weighted BCE) weighs the endpoints of its pairs with the same function.
+#include "ptw.h"
 #include <cmath>
 #include <type_traits>
 
 namespace hgnn {
 namespace {
 
-constexpr int kPhMaxGrid = 2048;   // 256 CUs x 8 workgroups: cap, then grid-stride
 constexpr int kPhAcc = 4;          // S_T, S_F, L_T, L_F
 
 struct PhParams {
-    float wmin, one_minus_wmin, leak, cut, cap, interval;   // pt_weighting
+    float wmin, one_minus_wmin, leak, cut, cap, interval;   // pt_weighting (ptw_fill)
     float margin, scale;
 };
-
-}  // namespace
-}  // namespace hgnn
-// ph_ptw(pt, params): pt_weighting in float32 with a NaN pt read as 0.  It lives in a header of its own because
-// k_wb_* (wbce.hip, the weighted BCE) weighs the endpoints of its pairs with the same function.
-#include "ptw.h"
-namespace hgnn {
-namespace {
 
 template <bool V4>
 __device__ __forceinline__ float ph_dist(const float* __restrict__ E, int64_t a, int64_t b, int D) {
@@ -59,38 +55,6 @@ __device__ __forceinline__ float ph_dist(const float* __restrict__ E, int64_t a,
     return sqrtf(s + 1e-12f);
 }
 
-// the ids of VEC = 16 / sizeof(IT) consecutive pairs as one 16-byte load per endpoint row
-template <class IT>
-struct alignas(16) PhIds {
-    IT v[16 / sizeof(IT)];
-};
-
-template <class IT, bool VEC_OK>
-__device__ __forceinline__ void ph_load_ids(const IT* __restrict__ row, int64_t first, int n, int64_t* out) {
-    constexpr int VEC = 16 / sizeof(IT);
-    if (VEC_OK && n == VEC) {
-        const PhIds<IT> t = *reinterpret_cast<const PhIds<IT>*>(row + first);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) out[j] = (int64_t)t.v[j];
-    } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) out[j] = j < n ? (int64_t)row[first + j] : 0;
-    }
-}
-
-// fixed-shape sum of one double per thread over the workgroup: xor tree inside the wave, then the waves in order
-__device__ __forceinline__ double ph_block_sum(double v, double* lds) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    const int wave = threadIdx.x / kWave;
-    __syncthreads();
-    if (threadIdx.x % kWave == 0) lds[wave] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < kWavesPerBlock; ++w) t += lds[w];
-    return t;
-}
-
 template <class IT, bool VEC_OK, bool V4>
 __global__ __launch_bounds__(kBlock) void k_ph_forward(const float* __restrict__ E, int64_t N, int D,
                                                        const IT* __restrict__ ga, const IT* __restrict__ gb,
@@ -106,8 +70,8 @@ __global__ __launch_bounds__(kBlock) void k_ph_forward(const float* __restrict__
         const int64_t first = g * VEC;
         const int n = (int)(P - first < VEC ? P - first : VEC);
         int64_t a[VEC], b[VEC];
-        ph_load_ids<IT, VEC_OK>(ga, first, n, a);
-        ph_load_ids<IT, VEC_OK>(gb, first, n, b);
+        load_pair_ids<IT, VEC_OK>(ga, first, n, a);
+        load_pair_ids<IT, VEC_OK>(gb, first, n, b);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
             if (j >= n) break;
@@ -127,8 +91,8 @@ __global__ __launch_bounds__(kBlock) void k_ph_forward(const float* __restrict__
         }
     }
     if (bad) atomicOr(status, 1);
-    for (int k = 0; k < kPhAcc; ++k) {
-        const double s = ph_block_sum(acc[k], lds);
+    for (int k = 0; k < kPhAcc; ++k) {                       // det_reduce.h write_partials: the same layout
+        const double s = block_sum(acc[k], lds);
         if (threadIdx.x == 0) partials[(int64_t)k * gridDim.x + blockIdx.x] = s;
     }
 }
@@ -140,10 +104,10 @@ __global__ __launch_bounds__(kBlock) void k_ph_finish(const double* __restrict__
                                                       float* __restrict__ loss) {
     __shared__ double lds[kWavesPerBlock];
     double tot[kPhAcc];
-    for (int k = 0; k < kPhAcc; ++k) {
+    for (int k = 0; k < kPhAcc; ++k) {                       // det_reduce.h total_partials: the same order
         double v = 0.0;
         for (int j = threadIdx.x; j < n_partials; j += kBlock) v += partials[(int64_t)k * n_partials + j];
-        tot[k] = ph_block_sum(v, lds);
+        tot[k] = block_sum(v, lds);
     }
     if (threadIdx.x == 0) {
         const double kt = tot[0] > 0.0 ? sig_t / tot[0] : 0.0;
@@ -174,8 +138,8 @@ __global__ __launch_bounds__(kBlock) void k_ph_coef(const float* __restrict__ E,
         const int64_t first = g * VEC;
         const int n = (int)(P - first < VEC ? P - first : VEC);
         int64_t a[VEC], b[VEC];
-        ph_load_ids<IT, VEC_OK>(ga, first, n, a);
-        ph_load_ids<IT, VEC_OK>(gb, first, n, b);
+        load_pair_ids<IT, VEC_OK>(ga, first, n, a);
+        load_pair_ids<IT, VEC_OK>(gb, first, n, b);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
             if (j >= n) break;
@@ -248,11 +212,6 @@ __global__ __launch_bounds__(kBlock) void k_ph_grad(const float* __restrict__ E,
     }
 }
 
-unsigned ph_grid(int64_t P, int vec) {
-    const int64_t blocks = ceil_div(ceil_div(P, vec), kBlock);
-    return (unsigned)(blocks < 1 ? 1 : (blocks > kPhMaxGrid ? kPhMaxGrid : blocks));
-}
-
 struct PhScratch {
     size_t partials, coef, total;
 };
@@ -264,7 +223,7 @@ void ph_layout(int64_t P, int backward, PhScratch* s) {
         off = align_up(off + bytes, 256);
         return o;
     };
-    s->partials = take((size_t)kPhAcc * kPhMaxGrid * sizeof(double));
+    s->partials = take((size_t)kPhAcc * kDetMaxGrid * sizeof(double));
     s->coef = backward ? take((size_t)P * sizeof(float)) : 0;
     s->total = off;
 }
@@ -281,12 +240,7 @@ int ph_check(const char* what, const void* E, int64_t N, int32_t D, const void* 
 
 PhParams ph_params(const double* h) {
     PhParams q;
-    q.wmin = (float)h[HGNN_PH_WEIGHT_MIN];
-    q.one_minus_wmin = (float)(1.0 - h[HGNN_PH_WEIGHT_MIN]);
-    q.leak = (float)h[HGNN_PH_WEIGHT_LEAK];
-    q.cut = (float)(h[HGNN_PH_PTCUT] - h[HGNN_PH_PT_INTERVAL]);
-    q.cap = (float)h[HGNN_PH_PTCUT];
-    q.interval = (float)(h[HGNN_PH_PTCUT] - (h[HGNN_PH_PTCUT] - h[HGNN_PH_PT_INTERVAL]));
+    ptw_fill(q, h);
     q.margin = (float)h[HGNN_PH_MARGIN];
     q.scale = (float)h[HGNN_PH_SCALE];
     return q;
@@ -295,19 +249,11 @@ PhParams ph_params(const double* h) {
 // fn(index type tag, VEC_OK, V4): the three compile-time choices of the per-pair kernels
 template <class Fn>
 void ph_dispatch(const void* E, int D, const void* graph, int64_t P, int32_t index_dtype, Fn&& fn) {
-    const size_t isz = index_dtype == HGNN_DT_I64 ? 8 : 4;
-    const bool vec_ok = (uintptr_t)graph % 16 == 0 && ((size_t)P * isz) % 16 == 0;
     const bool v4 = D % 4 == 0 && (uintptr_t)E % 16 == 0;
-    auto with_v4 = [&](auto it, auto vk) {
+    with_index_type(index_dtype, graph, P, [&](auto it, auto vk) {
         if (v4) fn(it, vk, std::true_type{});
         else fn(it, vk, std::false_type{});
-    };
-    auto with_vec = [&](auto it) {
-        if (vec_ok) with_v4(it, std::true_type{});
-        else with_v4(it, std::false_type{});
-    };
-    if (index_dtype == HGNN_DT_I64) with_vec((int64_t)0);
-    else with_vec((int32_t)0);
+    });
 }
 
 }  // namespace
@@ -335,20 +281,17 @@ extern "C" int hgnn_pair_hinge_forward(const float* E, int64_t N, int32_t D, con
     HGNN_REQUIRE(hparams && loss && state && status, "hgnn_pair_hinge_forward: NULL pointer");
     PhScratch s;
     ph_layout(P, 0, &s);
-    if (workspace_bytes < s.total || workspace == nullptr) {
-        set_error("hgnn_pair_hinge_forward: workspace too small (%zu < %zu)", workspace_bytes, s.total);
-        return HGNN_ERR_WORKSPACE;
-    }
+    HGNN_REQUIRE_WORKSPACE("hgnn_pair_hinge_forward", workspace, workspace_bytes, s.total);
     double* partials = (double*)((char*)workspace + s.partials);
     const PhParams q = ph_params(hparams);
-    const double lwr = hparams[HGNN_PH_LOG_WEIGHT_RATIO];
-    const double sig_t = 1.0 / (1.0 + exp(-lwr)), sig_f = 1.0 / (1.0 + exp(lwr));
+    double sig_t, sig_f;
+    class_sigmoids(hparams[HGNN_PH_LOG_WEIGHT_RATIO], &sig_t, &sig_f);
     HGNN_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), stream));
     int n_partials = 0;
     if (P > 0) {
         ph_dispatch(E, D, graph, P, index_dtype, [&](auto it, auto vk, auto v4) {
             using IT = decltype(it);
-            const unsigned grid = ph_grid(P, 16 / sizeof(IT));
+            const unsigned grid = det_grid(ceil_div(P, 16 / sizeof(IT)));
             n_partials = (int)grid;
             k_ph_forward<IT, decltype(vk)::value, decltype(v4)::value><<<grid, kBlock, 0, stream>>>(
                 E, N, D, (const IT*)graph, (const IT*)graph + P, y, pt, P, q, partials, status);
@@ -379,15 +322,13 @@ extern "C" int hgnn_pair_hinge_backward(const hgnn_plan* plan, const float* E, i
     HGNN_REQUIRE(plan->rowptr && plan->perm && plan->src_row, "hgnn_pair_hinge_backward: a plan array is NULL");
     PhScratch s;
     ph_layout(P, 1, &s);
-    if (workspace_bytes < s.total || workspace == nullptr) {
-        set_error("hgnn_pair_hinge_backward: workspace too small (%zu < %zu)", workspace_bytes, s.total);
-        return HGNN_ERR_WORKSPACE;
-    }
+    HGNN_REQUIRE_WORKSPACE("hgnn_pair_hinge_backward", workspace, workspace_bytes, s.total);
     float* coef = (float*)((char*)workspace + s.coef);
     const PhParams q = ph_params(hparams);
     ph_dispatch(E, D, graph, P, index_dtype, [&](auto it, auto vk, auto v4) {
         using IT = decltype(it);
-        k_ph_coef<IT, decltype(vk)::value, decltype(v4)::value><<<ph_grid(P, 16 / sizeof(IT)), kBlock, 0, stream>>>(
+        const unsigned grid = det_grid(ceil_div(P, 16 / sizeof(IT)));
+        k_ph_coef<IT, decltype(vk)::value, decltype(v4)::value><<<grid, kBlock, 0, stream>>>(
             E, N, D, (const IT*)graph, (const IT*)graph + P, y, pt, P, q, state, grad_out, coef);
     });
     const unsigned grad_grid = (unsigned)ceil_div(N * kPhLanes, kBlock);

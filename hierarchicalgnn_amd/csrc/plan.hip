@@ -239,10 +239,7 @@ extern "C" int hgnn_plan_item_order(const hgnn_plan* plan, int32_t* order, void*
     OrderScratch s;
     int rc = order_scratch_layout(plan, &s, stream);
     if (rc != HGNN_OK) return rc;
-    if (workspace_bytes < s.total || workspace == nullptr) {
-        set_error("hgnn_plan_item_order: workspace too small (%zu < %zu)", workspace_bytes, s.total);
-        return HGNN_ERR_WORKSPACE;
-    }
+    HGNN_REQUIRE_WORKSPACE("hgnn_plan_item_order", workspace, workspace_bytes, s.total);
     char* ws = (char*)workspace;
     int32_t* keys_in = (int32_t*)(ws + s.keys_in);
     int32_t* keys_out = (int32_t*)(ws + s.keys_out);

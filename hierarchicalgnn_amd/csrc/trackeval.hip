@@ -459,10 +459,7 @@ extern "C" int hgnn_track_eval(const int64_t* hit, const int64_t* cand, int64_t 
     TeWorkspace w;
     rc = te_layout(n_pairs, n_hits, &w, stream);
     if (rc != HGNN_OK) return rc;
-    if (workspace_bytes < w.total || workspace == nullptr) {
-        set_error("hgnn_track_eval: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-        return HGNN_ERR_WORKSPACE;
-    }
+    HGNN_REQUIRE_WORKSPACE("hgnn_track_eval", workspace, workspace_bytes, w.total);
     char* ws = (char*)workspace;
     auto I32 = [&](size_t o) { return (int32_t*)(ws + o); };
     const int B = (int)n_pairs, N = (int)n_hits;

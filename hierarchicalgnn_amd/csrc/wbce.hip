@@ -11,11 +11,13 @@
 //
 // Forward: ONE pass over the pairs (k_wb_forward) that accumulates the four sums in float64 -- per thread in a fixed
 // order, per workgroup through a fixed tree -- and writes one partial per workgroup; k_wb_finish adds the partials in
-// index order.  The grid is a function of P alone, so the bits are too.  The class normalisation is applied to the
-// sums: no [P] weight vector exists.  Backward: one elementwise pass (k_wb_backward) that recomputes raw_i and writes
-// every element of grad_scores; no atomics, no plan.
+// index order.  The grid is a function of P alone, so the bits are too: the tree, the grid and the id loader are
+// det_reduce.h's.  The class normalisation is applied to the sums: no [P] weight vector exists.
+// Backward: one elementwise pass (k_wb_backward) that recomputes raw_i and writes every element of grad_scores; no
+// atomics, no plan.
 // Streams per pair: the two ids, the score, y and keep (if given).  The pt tables stay cache-resident.
 #include "common.h"
+#include "det_reduce.h"
 #include "ptw.h"
 #include <cmath>
 #include <type_traits>
@@ -23,44 +25,11 @@
 namespace hgnn {
 namespace {
 
-constexpr int kWbMaxGrid = 2048;   // 256 CUs x 8 workgroups: cap, then grid-stride
 constexpr int kWbAcc = 4;          // S_T, S_F, L_T, L_F
 
 struct WbParams {
-    float wmin, one_minus_wmin, leak, cut, cap, interval;   // pt_weighting
+    float wmin, one_minus_wmin, leak, cut, cap, interval;   // pt_weighting (ptw_fill)
 };
-
-// the ids of VEC = 16 / sizeof(IT) consecutive pairs as one 16-byte load per endpoint row
-template <class IT>
-struct alignas(16) WbIds {
-    IT v[16 / sizeof(IT)];
-};
-
-template <class IT, bool VEC_OK>
-__device__ __forceinline__ void wb_load_ids(const IT* __restrict__ row, int64_t first, int n, int64_t* out) {
-    constexpr int VEC = 16 / sizeof(IT);
-    if (VEC_OK && n == VEC) {
-        const WbIds<IT> t = *reinterpret_cast<const WbIds<IT>*>(row + first);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) out[j] = (int64_t)t.v[j];
-    } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) out[j] = j < n ? (int64_t)row[first + j] : 0;
-    }
-}
-
-// fixed-shape sum of one double per thread over the workgroup: xor tree inside the wave, then the waves in order
-__device__ __forceinline__ double wb_block_sum(double v, double* lds) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    const int wave = threadIdx.x / kWave;
-    __syncthreads();
-    if (threadIdx.x % kWave == 0) lds[wave] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < kWavesPerBlock; ++w) t += lds[w];
-    return t;
-}
 
 // raw_i, or false for a pair that takes no part: dropped by keep, or skipped with its status bit set in *bad
 template <bool MAX>
@@ -101,8 +70,8 @@ __global__ __launch_bounds__(kBlock) void k_wb_forward(const float* __restrict__
         const int64_t first = g * VEC;
         const int n = (int)(P - first < VEC ? P - first : VEC);
         int64_t a[VEC], b[VEC];
-        wb_load_ids<IT, VEC_OK>(ga, first, n, a);
-        wb_load_ids<IT, VEC_OK>(gb, first, n, b);
+        load_pair_ids<IT, VEC_OK>(ga, first, n, a);
+        load_pair_ids<IT, VEC_OK>(gb, first, n, b);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
             if (j >= n) break;
@@ -118,8 +87,8 @@ __global__ __launch_bounds__(kBlock) void k_wb_forward(const float* __restrict__
         }
     }
     if (bad) atomicOr(status, bad);
-    for (int k = 0; k < kWbAcc; ++k) {
-        const double s = wb_block_sum(acc[k], lds);
+    for (int k = 0; k < kWbAcc; ++k) {                       // det_reduce.h write_partials: the same layout
+        const double s = block_sum(acc[k], lds);
         if (threadIdx.x == 0) partials[(int64_t)k * gridDim.x + blockIdx.x] = s;
     }
 }
@@ -131,10 +100,10 @@ __global__ __launch_bounds__(kBlock) void k_wb_finish(const double* __restrict__
                                                       float* __restrict__ loss) {
     __shared__ double lds[kWavesPerBlock];
     double tot[kWbAcc];
-    for (int k = 0; k < kWbAcc; ++k) {
+    for (int k = 0; k < kWbAcc; ++k) {                       // det_reduce.h total_partials: the same order
         double v = 0.0;
         for (int j = threadIdx.x; j < n_partials; j += kBlock) v += partials[(int64_t)k * n_partials + j];
-        tot[k] = wb_block_sum(v, lds);
+        tot[k] = block_sum(v, lds);
     }
     if (threadIdx.x == 0) {
         const double kt = tot[0] > 0.0 ? sig_t / tot[0] : 0.0;
@@ -169,8 +138,8 @@ __global__ __launch_bounds__(kBlock) void k_wb_backward(const float* __restrict_
         const int64_t first = g * VEC;
         const int n = (int)(P - first < VEC ? P - first : VEC);
         int64_t a[VEC], b[VEC];
-        wb_load_ids<IT, VEC_OK>(ga, first, n, a);
-        wb_load_ids<IT, VEC_OK>(gb, first, n, b);
+        load_pair_ids<IT, VEC_OK>(ga, first, n, a);
+        load_pair_ids<IT, VEC_OK>(gb, first, n, b);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
             if (j >= n) break;
@@ -185,12 +154,7 @@ __global__ __launch_bounds__(kBlock) void k_wb_backward(const float* __restrict_
     }
 }
 
-unsigned wb_grid(int64_t P, int vec) {
-    const int64_t blocks = ceil_div(ceil_div(P, vec), kBlock);
-    return (unsigned)(blocks < 1 ? 1 : (blocks > kWbMaxGrid ? kWbMaxGrid : blocks));
-}
-
-constexpr size_t kWbForwardBytes = (size_t)kWbAcc * kWbMaxGrid * sizeof(double);   // the partials
+constexpr size_t kWbForwardBytes = (size_t)kWbAcc * kDetMaxGrid * sizeof(double);   // the partials
 
 int wb_check(const char* what, const void* scores, const void* graph, int32_t index_dtype, const void* y,
              const void* pt_a, int64_t NA, const void* pt_b, int64_t NB, int64_t P, int32_t combine) {
@@ -205,30 +169,17 @@ int wb_check(const char* what, const void* scores, const void* graph, int32_t in
 
 WbParams wb_params(const double* h) {
     WbParams q;
-    q.wmin = (float)h[HGNN_PH_WEIGHT_MIN];
-    q.one_minus_wmin = (float)(1.0 - h[HGNN_PH_WEIGHT_MIN]);
-    q.leak = (float)h[HGNN_PH_WEIGHT_LEAK];
-    q.cut = (float)(h[HGNN_PH_PTCUT] - h[HGNN_PH_PT_INTERVAL]);
-    q.cap = (float)h[HGNN_PH_PTCUT];
-    q.interval = (float)(h[HGNN_PH_PTCUT] - (h[HGNN_PH_PTCUT] - h[HGNN_PH_PT_INTERVAL]));
+    ptw_fill(q, h);
     return q;
 }
 
 // fn(index type tag, VEC_OK, MAX): the three compile-time choices of the per-pair kernels
 template <class Fn>
 void wb_dispatch(const void* graph, int64_t P, int32_t index_dtype, int32_t combine, Fn&& fn) {
-    const size_t isz = index_dtype == HGNN_DT_I64 ? 8 : 4;
-    const bool vec_ok = (uintptr_t)graph % 16 == 0 && ((size_t)P * isz) % 16 == 0;
-    auto with_max = [&](auto it, auto vk) {
+    with_index_type(index_dtype, graph, P, [&](auto it, auto vk) {
         if (combine == HGNN_WB_COMBINE_MAX) fn(it, vk, std::true_type{});
         else fn(it, vk, std::false_type{});
-    };
-    auto with_vec = [&](auto it) {
-        if (vec_ok) with_max(it, std::true_type{});
-        else with_max(it, std::false_type{});
-    };
-    if (index_dtype == HGNN_DT_I64) with_vec((int64_t)0);
-    else with_vec((int32_t)0);
+    });
 }
 
 }  // namespace
@@ -252,20 +203,17 @@ extern "C" int hgnn_weighted_bce_forward(const float* scores, const void* graph,
     int rc = wb_check("hgnn_weighted_bce_forward", scores, graph, index_dtype, y, pt_a, NA, pt_b, NB, P, combine);
     if (rc != HGNN_OK) return rc;
     HGNN_REQUIRE(hparams && loss && state && status, "hgnn_weighted_bce_forward: NULL pointer");
-    if (workspace_bytes < kWbForwardBytes || workspace == nullptr) {
-        set_error("hgnn_weighted_bce_forward: workspace too small (%zu < %zu)", workspace_bytes, kWbForwardBytes);
-        return HGNN_ERR_WORKSPACE;
-    }
+    HGNN_REQUIRE_WORKSPACE("hgnn_weighted_bce_forward", workspace, workspace_bytes, kWbForwardBytes);
     double* partials = (double*)workspace;
     const WbParams q = wb_params(hparams);
-    const double lwr = hparams[HGNN_PH_LOG_WEIGHT_RATIO];
-    const double sig_t = 1.0 / (1.0 + exp(-lwr)), sig_f = 1.0 / (1.0 + exp(lwr));
+    double sig_t, sig_f;
+    class_sigmoids(hparams[HGNN_PH_LOG_WEIGHT_RATIO], &sig_t, &sig_f);
     HGNN_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), stream));
     int n_partials = 0;
     if (P > 0) {
         wb_dispatch(graph, P, index_dtype, combine, [&](auto it, auto vk, auto mx) {
             using IT = decltype(it);
-            const unsigned grid = wb_grid(P, 16 / sizeof(IT));
+            const unsigned grid = det_grid(ceil_div(P, 16 / sizeof(IT)));
             n_partials = (int)grid;
             k_wb_forward<IT, decltype(vk)::value, decltype(mx)::value><<<grid, kBlock, 0, stream>>>(
                 scores, (const IT*)graph, (const IT*)graph + P, y, keep, pt_a, NA, pt_b, NB, P, q, partials, status);
@@ -290,10 +238,10 @@ extern "C" int hgnn_weighted_bce_backward(const float* scores, const void* graph
     const WbParams q = wb_params(hparams);
     wb_dispatch(graph, P, index_dtype, combine, [&](auto it, auto vk, auto mx) {
         using IT = decltype(it);
-        k_wb_backward<IT, decltype(vk)::value, decltype(mx)::value>
-            <<<wb_grid(P, 16 / sizeof(IT)), kBlock, 0, stream>>>(scores, (const IT*)graph, (const IT*)graph + P, y,
-                                                                 keep, pt_a, NA, pt_b, NB, P, q, state, grad_out,
-                                                                 grad_scores);
+        const unsigned grid = det_grid(ceil_div(P, 16 / sizeof(IT)));
+        k_wb_backward<IT, decltype(vk)::value, decltype(mx)::value><<<grid, kBlock, 0, stream>>>(
+            scores, (const IT*)graph, (const IT*)graph + P, y, keep, pt_a, NA, pt_b, NB, P, q, state, grad_out,
+            grad_scores);
     });
     HGNN_CHECK_HIP(hipGetLastError());
     return HGNN_OK;

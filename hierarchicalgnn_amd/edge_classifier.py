@@ -20,8 +20,6 @@ nothing where the reference's 0/0 makes the loss NaN.  There is no CPU path: inp
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
@@ -29,25 +27,11 @@ from .embedding import _field
 
 stats = {"host_reads": 0}
 
-_wb_pending = {}   # device -> int32[1]: the status words of the calls nobody has read yet, OR-ed on the device
+_wb_pending = _lib.PendingStatus(stats)
 _COMBINE = {"sum": _lib.WB_COMBINE_SUM, "max": _lib.WB_COMBINE_MAX}
 
 
-def _wb_scalars(hparams):
-    h = (ctypes.c_double * _lib.PH_HPARAMS)()
-    h[_lib.PH_WEIGHT_MIN] = float(hparams["weight_min"])
-    h[_lib.PH_WEIGHT_LEAK] = float(hparams["weight_leak"])
-    h[_lib.PH_PTCUT] = float(hparams["ptcut"])
-    h[_lib.PH_PT_INTERVAL] = float(hparams["pt_interval"])
-    h[_lib.PH_LOG_WEIGHT_RATIO] = float(hparams["log_weight_ratio"])
-    return h
-
-
-def _wb_workspace(p, backward, dev):
-    nb = ctypes.c_size_t(0)
-    _lib.check(_lib.load().hgnn_weighted_bce_workspace_bytes(p, backward, ctypes.byref(nb)),
-               "hgnn_weighted_bce_workspace_bytes")
-    return torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev), int(nb.value)
+_wb_scalars = _lib.pt_scalars
 
 
 class _WeightedBCE(torch.autograd.Function):
@@ -56,11 +40,11 @@ class _WeightedBCE(torch.autograd.Function):
         lib = _lib.load()
         dev = scores.device
         p = int(scores.numel())
-        idt = _lib.DT_I64 if graph.dtype == torch.int64 else _lib.DT_I32
+        idt = _lib.index_dtype(graph)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         state = torch.empty(_lib.WB_STATE, dtype=torch.float64, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
-        ws, nb = _wb_workspace(p, 0, dev)
+        ws, nb = _lib.workspace("hgnn_weighted_bce_workspace_bytes", dev, p, 0)
         with torch.cuda.device(dev):
             _lib.check(lib.hgnn_weighted_bce_forward(_lib.ptr(scores), _lib.ptr(graph), idt, _lib.ptr(y8),
                                                      _lib.ptr(keep8), _lib.ptr(pt_a), int(pt_a.numel()),
@@ -95,17 +79,7 @@ def weighted_bce_check(device=None):
     """Reads (ONE host read per device, counted in ``stats["host_reads"]``) and clears the status words of the
     ``weighted_bce_loss`` calls made since the last check: ValueError if any of them saw a pair id out of range or a
     score that is NaN or outside [0, 1]."""
-    if device is None:
-        devs = list(_wb_pending)
-    else:
-        dev = torch.device(device)
-        devs = [dev if dev.index is not None else torch.device(dev.type, torch.cuda.current_device())]
-    word = 0
-    for dev in devs:
-        pending = _wb_pending.pop(dev, None)
-        if pending is not None:
-            stats["host_reads"] += 1
-            word |= int(pending.item())
+    word = _wb_pending.take(device)
     if word & _lib.WB_ST_BAD_ID:
         raise ValueError("weighted_bce_loss: a pair id is negative or >= the length of its pt table")
     if word & _lib.WB_ST_BAD_SCORE:
@@ -147,8 +121,7 @@ def _wb_apply(scores, graph, y, pt_a, hparams, pt_b, combine, keep):
         raise ValueError("weighted_bce_loss: scores, graph, y, keep and the pt tables must be on one device")
     loss, status, state = _WeightedBCE.apply(scores.contiguous(), graph.contiguous(), y8, keep8, pt_a, pt_b,
                                              _wb_scalars(hparams), _COMBINE[combine])
-    word = _wb_pending.get(dev)
-    _wb_pending[dev] = status if word is None else word | status
+    _wb_pending.add(dev, status)
     return loss, status, state
 
 

@@ -93,10 +93,7 @@ def graph_intersection(pred_graph, truth_graph, using_weights=False, weights_bid
             raise ValueError(f"graph_intersection: weights_bidir must be float32 or float64, got {w.dtype}")
         w = w.contiguous()
     lib = _lib.load()
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.hgnn_graph_intersection_workspace_bytes(ep, et, 1 if using_weights else 0, ctypes.byref(nb)),
-               "hgnn_graph_intersection_workspace_bytes")
-    ws = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev)
+    ws, nb = _lib.workspace("hgnn_graph_intersection_workspace_bytes", dev, ep, et, 1 if using_weights else 0)
     out_graph = torch.empty((2, ep), dtype=torch.int64, device=dev)
     out_y = torch.empty(ep, dtype=torch.uint8, device=dev)
     out_w = torch.empty(ep, dtype=w.dtype, device=dev) if using_weights else None
@@ -104,7 +101,7 @@ def graph_intersection(pred_graph, truth_graph, using_weights=False, weights_bid
     with torch.cuda.device(dev):
         _lib.check(lib.hgnn_graph_intersection(_lib.ptr(pred), ep, _lib.ptr(truth), et, _lib.ptr(w), wdt,
                                                _lib.ptr(out_graph), _lib.ptr(out_y), _lib.ptr(out_w), _lib.ptr(cs),
-                                               _lib.ptr(ws), int(nb.value), _lib.current_stream(dev)),
+                                               _lib.ptr(ws), nb, _lib.current_stream(dev)),
                    "hgnn_graph_intersection")
     stats["host_reads"] += 1
     u, status = cs.tolist()
@@ -191,26 +188,14 @@ def hinge_distance(embeddings, graph, y):
 
 
 # --------------------------------------------------------------------------- the fused pair hinge loss
-_ph_pending = {}   # device -> int32[1]: the status words of the calls nobody has read yet, OR-ed on the device
+_ph_pending = _lib.PendingStatus(stats)
 
 
 def _ph_scalars(hparams, margin, scale):
-    h = (ctypes.c_double * _lib.PH_HPARAMS)()
-    h[_lib.PH_WEIGHT_MIN] = float(hparams["weight_min"])
-    h[_lib.PH_WEIGHT_LEAK] = float(hparams["weight_leak"])
-    h[_lib.PH_PTCUT] = float(hparams["ptcut"])
-    h[_lib.PH_PT_INTERVAL] = float(hparams["pt_interval"])
-    h[_lib.PH_LOG_WEIGHT_RATIO] = float(hparams["log_weight_ratio"])
+    h = _lib.pt_scalars(hparams)
     h[_lib.PH_MARGIN] = float(hparams["train_r"] if margin is None else margin)
     h[_lib.PH_SCALE] = float(scale)
     return h
-
-
-def _ph_workspace(p, n, d, backward, dev):
-    nb = ctypes.c_size_t(0)
-    _lib.check(_lib.load().hgnn_pair_hinge_workspace_bytes(p, n, d, backward, ctypes.byref(nb)),
-               "hgnn_pair_hinge_workspace_bytes")
-    return torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev), int(nb.value)
 
 
 def _ph_plan(graph, n, cache):
@@ -234,11 +219,11 @@ class _PairHinge(torch.autograd.Function):
         lib = _lib.load()
         dev = emb.device
         n, d, p = int(emb.shape[0]), int(emb.shape[1]), int(graph.shape[1])
-        idt = _lib.DT_I64 if graph.dtype == torch.int64 else _lib.DT_I32
+        idt = _lib.index_dtype(graph)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         state = torch.empty(_lib.PH_STATE, dtype=torch.float64, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
-        ws, nb = _ph_workspace(p, n, d, 0, dev)
+        ws, nb = _lib.workspace("hgnn_pair_hinge_workspace_bytes", dev, p, n, d, 0)
         with torch.cuda.device(dev):
             _lib.check(lib.hgnn_pair_hinge_forward(_lib.ptr(emb), n, d, _lib.ptr(graph), idt, _lib.ptr(y8),
                                                    _lib.ptr(pt), p, scalars, _lib.ptr(loss), _lib.ptr(state),
@@ -261,7 +246,7 @@ class _PairHinge(torch.autograd.Function):
         n, d, p = int(emb.shape[0]), int(emb.shape[1]), int(graph.shape[1])
         g = grad_loss.detach().reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_like(emb)
-        ws, nb = _ph_workspace(p, n, d, 1, dev)
+        ws, nb = _lib.workspace("hgnn_pair_hinge_workspace_bytes", dev, p, n, d, 1)
         with torch.cuda.device(dev):
             _lib.check(lib.hgnn_pair_hinge_backward(ctypes.byref(ctx.plan.c) if ctx.plan is not None else None,
                                                     _lib.ptr(emb), n, d, _lib.ptr(graph), ctx.idt, _lib.ptr(y8),
@@ -274,18 +259,7 @@ class _PairHinge(torch.autograd.Function):
 def pair_hinge_check(device=None):
     """Reads (ONE host read per device, counted in ``stats["host_reads"]``) and clears the status words of the
     ``pair_hinge_loss`` calls made since the last check: ValueError if any of them saw a pair id outside [0, N)."""
-    if device is None:
-        devs = list(_ph_pending)
-    else:
-        dev = torch.device(device)
-        devs = [dev if dev.index is not None else torch.device(dev.type, torch.cuda.current_device())]
-    bad = False
-    for dev in devs:
-        word = _ph_pending.pop(dev, None)
-        if word is not None:
-            stats["host_reads"] += 1
-            bad = bool(word.item()) or bad
-    if bad:
+    if _ph_pending.take(device):
         raise ValueError("pair_hinge_loss: a pair id is negative or >= the number of embedding rows")
 
 
@@ -322,8 +296,7 @@ def pair_hinge_loss(embeddings, graph, y, batch, hparams, margin=None, scale=1.0
     y8 = y.contiguous().view(torch.uint8)
     loss, status = _PairHinge.apply(embeddings.contiguous(), graph.contiguous(), y8, pt.detach().reshape(-1).contiguous(),
                                     _ph_scalars(hparams, margin, scale), bool(cache_plan))
-    word = _ph_pending.get(dev)
-    _ph_pending[dev] = status if word is None else word | status
+    _ph_pending.add(dev, status)
     if check:
         pair_hinge_check(dev)
     return loss

@@ -18,8 +18,6 @@ hand-written backward (csrc/graphcon.hip), no host read.  ``stats["host_reads"]`
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn as nn
 
@@ -72,13 +70,6 @@ def batch_norm_1(bn: nn.BatchNorm1d, x: torch.Tensor, stat_reduce=None) -> torch
     return y
 
 
-def _ga_workspace(e, backward, dev):
-    nb = ctypes.c_size_t(0)
-    _lib.check(_lib.load().hgnn_graph_attention_workspace_bytes(e, backward, ctypes.byref(nb)),
-               "hgnn_graph_attention_workspace_bytes")
-    return torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev), int(nb.value)
-
-
 class _GraphAttention(torch.autograd.Function):
     """(weights, logits, x, state) of hgnn_graph_attention_forward; backward: hgnn_graph_attention_backward for
     d/dx, d/dgamma, d/dbeta, then the weighted segmented reduce of ``_EdgeDot.backward`` for dA and dB"""
@@ -88,12 +79,12 @@ class _GraphAttention(torch.autograd.Function):
         lib = _lib.load()
         dev = A.device
         e = int(graph.shape[1])
-        idt = _lib.DT_I64 if graph.dtype == torch.int64 else _lib.DT_I32
+        idt = _lib.index_dtype(graph)
         A_c, B_c = _f32(A).contiguous(), _f32(B).contiguous()      # bf16 rows are widened once, as in _edge_dot
         x = torch.empty(e, dtype=torch.float32, device=dev)
         logits, weights = torch.empty_like(x), torch.empty_like(x)
         state = torch.empty(_lib.GA_STATE, dtype=torch.float64, device=dev)
-        ws, nb = _ga_workspace(e, 0, dev)
+        ws, nb = _lib.workspace("hgnn_graph_attention_workspace_bytes", dev, e, 0)
         momentum = -1.0 if bn.momentum is None else float(bn.momentum)
         with torch.cuda.device(dev):
             _lib.check(lib.hgnn_graph_attention_forward(
@@ -124,7 +115,7 @@ class _GraphAttention(torch.autograd.Function):
         g_l = None if g_logits is None else g_logits.to(torch.float32).contiguous()
         g_x = torch.empty_like(x)
         g_bn = torch.empty(2, dtype=torch.float32, device=dev)
-        ws, nb = _ga_workspace(e, 1, dev)
+        ws, nb = _lib.workspace("hgnn_graph_attention_workspace_bytes", dev, e, 1)
         with torch.cuda.device(dev):
             _lib.check(lib.hgnn_graph_attention_backward(
                 _lib.ptr(x), e, _lib.ptr(gamma), _lib.ptr(beta), ctx.flags, ctx.fn, _lib.ptr(state), _lib.ptr(g_w),

@@ -43,9 +43,7 @@ def hdbscan_tree(points: torch.Tensor, min_cluster_size: int = 5, min_samples=No
     dev = points.device
     x = points.detach().contiguous()
     lib = _lib.load()
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.hgnn_hdbscan_workspace_bytes(n, d, mcs, ms, ctypes.byref(nb)), "hgnn_hdbscan_workspace_bytes")
-    ws = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev)
+    ws, nb = _lib.workspace("hgnn_hdbscan_workspace_bytes", dev, n, d, mcs, ms)
     labels = torch.empty(n, dtype=torch.int64, device=dev)
     edges = torch.empty((n - 1, 2), dtype=torch.int64, device=dev)
     w2 = torch.empty(n - 1, dtype=torch.float32, device=dev)
@@ -54,7 +52,7 @@ def hdbscan_tree(points: torch.Tensor, min_cluster_size: int = 5, min_samples=No
     info[_lib.HDB_STAGE_SYNC] = 1 if stage_sync else 0
     with torch.cuda.device(dev):
         _lib.check(lib.hgnn_hdbscan_f32(_lib.ptr(x), n, d, mcs, ms, _lib.ptr(labels), _lib.ptr(edges), _lib.ptr(w2),
-                                        _lib.ptr(core2), info, _lib.ptr(ws), int(nb.value),
+                                        _lib.ptr(core2), info, _lib.ptr(ws), nb,
                                         _lib.current_stream(dev)), "hgnn_hdbscan_f32")
     rounds = int(info[_lib.HDB_ROUNDS])
     stats["calls"] += 1

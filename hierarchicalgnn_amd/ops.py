@@ -594,15 +594,12 @@ def knn_edges(idx: torch.Tensor, n_pts: int, sym: bool = False) -> torch.Tensor:
         return torch.empty((2, 0), dtype=torch.int64, device=dev)
     idx_c = idx.detach().contiguous()
     lib = _lib.load()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.hgnn_knn_edges_workspace_bytes(nq, K, n_pts, int(bool(sym)), ctypes.byref(nbytes)),
-               "hgnn_knn_edges_workspace_bytes")
-    ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=dev)
+    ws, nbytes = _lib.workspace("hgnn_knn_edges_workspace_bytes", dev, nq, K, n_pts, int(bool(sym)))
     edges = torch.empty((2, cap), dtype=torch.int64, device=dev)
     info = torch.empty(2, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.hgnn_knn_edges(_lib.ptr(idx_c), nq, K, n_pts, int(bool(sym)), _lib.ptr(edges), cap,
-                                      _lib.ptr(info), _lib.ptr(ws), int(nbytes.value), _lib.current_stream(dev)),
+                                      _lib.ptr(info), _lib.ptr(ws), nbytes, _lib.current_stream(dev)),
                    "hgnn_knn_edges")
     gc_stats["host_reads"] += 1
     count, status = info.tolist()

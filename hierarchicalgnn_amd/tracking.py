@@ -19,7 +19,6 @@ There is no CPU path: every input must be a HIP device tensor.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
@@ -72,16 +71,13 @@ def track_eval(bipartite_graph: torch.Tensor, event, pt_cut: float = 1., nhits_c
     if pt.numel() != pid.numel() or (prim is not None and prim.numel() != pid.numel()):
         raise ValueError("eval_metrics: event.pid, event.pt (and event.primary) must have one entry per hit")
     lib = _lib.load()
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.hgnn_track_eval_workspace_bytes(hit.numel(), pid.numel(), ctypes.byref(nb)),
-               "hgnn_track_eval_workspace_bytes")
-    ws = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev)
+    ws, nb = _lib.workspace("hgnn_track_eval_workspace_bytes", dev, hit.numel(), pid.numel())
     result = torch.empty(_lib.TE_RESULT, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.hgnn_track_eval(_lib.ptr(hit), _lib.ptr(cand), hit.numel(), _lib.ptr(pid), _lib.ptr(pt),
                                        _lib.ptr(prim) if prim is not None else None, pid.numel(), float(pt_cut),
                                        float(nhits_cut), float(majority_cut), _lib.ptr(result), _lib.ptr(ws),
-                                       int(nb.value), _lib.current_stream(dev)), "hgnn_track_eval")
+                                       nb, _lib.current_stream(dev)), "hgnn_track_eval")
     return result
 
 

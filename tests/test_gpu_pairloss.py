@@ -87,7 +87,7 @@ def _loss64(e, graph, y, pt_t):
     loss = torch.empty(1, device=DEV)
     state = torch.empty(_lib.PH_STATE, dtype=torch.float64, device=DEV)
     status = torch.empty(1, dtype=torch.int32, device=DEV)
-    ws, nb = E._ph_workspace(g_t.shape[1], e.shape[0], e.shape[1], 0, e.device)
+    ws, nb = _lib.workspace("hgnn_pair_hinge_workspace_bytes", e.device, g_t.shape[1], e.shape[0], e.shape[1], 0)
     _lib.check(_lib.load().hgnn_pair_hinge_forward(
         _lib.ptr(e), e.shape[0], e.shape[1], _lib.ptr(g_t), _lib.DT_I64, _lib.ptr(y_t), _lib.ptr(pt_t), g_t.shape[1],
         E._ph_scalars(HP, None, 1.0), _lib.ptr(loss), _lib.ptr(state), _lib.ptr(status), _lib.ptr(ws), nb,

@@ -174,7 +174,7 @@ def _forward64(scores, graph, y, pt):
     loss = torch.empty(1, device=DEV)
     state = torch.empty(_lib.WB_STATE, dtype=torch.float64, device=DEV)
     status = torch.empty(1, dtype=torch.int32, device=DEV)
-    ws, nb = EC._wb_workspace(scores.numel(), 0, scores.device)
+    ws, nb = _lib.workspace("hgnn_weighted_bce_workspace_bytes", scores.device, scores.numel(), 0)
     y8 = y.view(torch.uint8)
     _lib.check(_lib.load().hgnn_weighted_bce_forward(
         _lib.ptr(scores), _lib.ptr(graph), _lib.DT_I64, _lib.ptr(y8), None, _lib.ptr(pt), pt.numel(), _lib.ptr(pt),
