@@ -19,6 +19,7 @@ HGNN_OK = 0
 CNT_WORK, CNT_SPLIT, CNT_PARTIAL, CNT_ERR, CNT_VALID, CNT_UNSORTED = 0, 1, 2, 3, 4, 5
 ABI_VERSION = 26
 MLP_BWD_BLOCKS = 512   # HGNN_MLP_BWD_BLOCKS
+MLP_BWD_TILE_ROWS_N1024 = 32   # HGNN_MLP_BWD_TILE_ROWS_N1024: rows per tile of the N = 1024 backward layer
 GMM_STATE, GMM_BLOCKS = 16, 1024   # HGNN_GMM_STATE, HGNN_GMM_BLOCKS
 LN_ACT_BLOCKS = 1024   # HGNN_LN_ACT_BLOCKS
 RED_SUM, RED_MIN, RED_MAX = 0, 1, 2   # HGNN_RED_*

@@ -10,7 +10,8 @@
 // i.e. the data-gradient GEMM of Modules/utils.py:169-196's Linear fused with the LayerNorm / activation backward of
 // the layer below it (unfused: one library GEMM writing da, one row pass reading z', da and writing dz', one more
 // recomputing a': 13 B/element of HBM traffic instead of 7).  The decomposition is the forward feature-split
-// kernel's (mlp_split_bf16.hip): a workgroup owns 64 rows, wave w a quarter of the N output features; the rows of dz
+// kernel's (mlp_split_bf16.hip): a workgroup owns 64 rows (32 at N = 1024), wave w a quarter of the N output features
+// (an eighth at N >= 512); the rows of dz
 // reach the MFMAs through LDS panels, W^T streams from L2 in A-fragment order through the register ring
 // (gemm_lds); the epilogue works in the accumulator layout (lane = row, registers = features):
 //   * z' is loaded in that layout as raw bf16 (2 registers per 4 values) and converted each time it is needed,
@@ -368,9 +369,11 @@ __global__ __launch_bounds__(NW * 64, MINB) void k_mlp_bwd_layer(const Args a) {
 
 constexpr int kBwdGrid = HGNN_MLP_BWD_BLOCKS;
 
-template <int NT, int EPI, int VAR, int MINB, int NW = 4, bool KEEPZ = true>
+template <int NT, int EPI, int VAR, int MINB, int NW = 4, bool KEEPZ = true, int NJ = 4>
 static int launch(const Args& a, hipStream_t s) {
-    constexpr int NJ = 4, TE = 64, N = NT * NW * 16;
+    constexpr int TE = 16 * NJ, N = NT * NW * 16;
+    static_assert(TE % (NW * 4) == 0 && NW * 64 <= 1024, "a panel pass of NW * 4 rows must divide the row tile");
+    static_assert(N != 1024 || TE == HGNN_MLP_BWD_TILE_ROWS_N1024, "the header's tile rows of the N = 1024 instance");
     const size_t lds = (size_t)2 * TE * (128 * 2 + 16) + NW * TE * 2 * sizeof(float) + (EPI == EPI_LN ? 2 * N * sizeof(float) : 0);
     const long long n_tiles = (a.M + TE - 1) / TE;
     // EPI_LN: a fixed grid (the partials are [HGNN_MLP_BWD_BLOCKS][2][N]; idle workgroups write zeros)
@@ -392,8 +395,14 @@ static int dispatch(const Args& a, int N, hipStream_t s) {
             // (round-2 null result, removed: 4 waves, 2 workgroups per CU, z' reloaded per phase -- the LayerNorm form
             // still spills 125 registers and measured 6.2 vs 3.2 ms at K = 256, M = 2M)
             return launch<4, EPI, 0, 1, 8>(a, s);
+        // N = 1024 (latent 512): 8 waves share a 32-row tile (NJ = 2, 8 feature tiles per wave, z' kept in registers):
+        // 64 accumulators + 32 raw-z' registers per lane as at N = 512, twice the L2 weight stream per row.  Resource
+        // usage (LayerNorm / input form): 235 / 138 registers, 27 / 19 KiB LDS, no scratch.  Tried and not shipped:
+        // 16 waves x 64 rows without KEEPZ (128-register budget: 136 / 11 registers spilled) and 8 waves x 64 rows
+        // without KEEPZ (128 accumulators: the LayerNorm form spills 123)
+        case 1024: return launch<8, EPI, 0, 1, 8, true, 2>(a, s);
     }
-    set_error("hgnn_mlp_backward_layer_bf16: N = %d has no instantiation (128, 256, 512)", N);
+    set_error("hgnn_mlp_backward_layer_bf16: N = %d has no instantiation (128, 256, 512, 1024)", N);
     return HGNN_ERR_UNSUPPORTED;
 }
 
@@ -403,7 +412,7 @@ static int dispatch(const Args& a, int N, hipStream_t s) {
 using namespace hgnn;
 
 extern "C" int hgnn_mlp_backward_layer_supported_bf16(int32_t K, int32_t N) {
-    return (K > 0 && K % 128 == 0 && (N == 128 || N == 256 || N == 512)) ? 1 : 0;
+    return (K > 0 && K % 128 == 0 && (N == 128 || N == 256 || N == 512 || N == 1024)) ? 1 : 0;
 }
 
 extern "C" int hgnn_mlp_backward_layer_bf16(const void* dz, int64_t M, int32_t K, int32_t N, const void* Wt_frag,
@@ -412,7 +421,7 @@ extern "C" int hgnn_mlp_backward_layer_bf16(const void* dz, int64_t M, int32_t K
                                             hgnn_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     HGNN_REQUIRE(hgnn_mlp_backward_layer_supported_bf16(K, N), "hgnn_mlp_backward_layer_bf16: unsupported shape K=%d N=%d "
-                 "(K a multiple of 128, N in {128, 256, 512})", K, N);
+                 "(K a multiple of 128, N in {128, 256, 512, 1024})", K, N);
     HGNN_REQUIRE(M >= 0 && M <= 0x7fffffffLL, "hgnn_mlp_backward_layer_bf16: bad M");
     const bool ln = z_prev != nullptr;
     HGNN_REQUIRE(!ln || (ln_w != nullptr && ln_b != nullptr && partials != nullptr && skip == nullptr),

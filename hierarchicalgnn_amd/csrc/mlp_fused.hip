@@ -403,8 +403,12 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_fused_mlp(const MlpArgs a) {
     if constexpr (NT2 == 0) {
         // single-layer launch (fp32 at latent 512: a 1024-wide hidden layer is 256 accumulators per lane, so the
         // layers of an MLP run as separate launches and the hidden rows make one trip through HBM)
-        if (!(a.ablate & 1)) layernorm_act<NT1, ACT_O>(acc1, a.lnw[0], a.lnb[0], a.act[0], a.eps, g);
-        store_out<NT1>(acc1, a, e, valid, g);
+        // PARTIAL: the layer is narrower than its zero-padded storage (504 of 512: the supernode encoder's last
+        // layer at latent 512): statistics over the real width with the padded features masked out, real-width store
+        if (!(a.ablate & 1))
+            layernorm_act<NT1, ACT_O, true, false, PARTIAL>(acc1, a.lnw[0], a.lnb[0], a.act[0], a.eps, g,
+                                                            PARTIAL ? a.n_out_real : NT1 * 16);
+        store_out<NT1, PARTIAL>(acc1, a, e, valid, g);
         return;
     }
     if (!(a.ablate & 1))
@@ -481,13 +485,13 @@ static int launch_mlp(const MlpArgs& a, hipStream_t s) {
 }
 
 // one Linear -> LayerNorm -> act (+ skip) layer: the pieces of an fp32 MLP at latent 512
-template <int NT1, int MINW>
+template <int NT1, int MINW, bool PARTIAL = false>
 static int launch_single(const MlpArgs& a, hipStream_t s) {
     switch (a.act[0]) {
-        case HGNN_ACT_GELU: return launch_mlp_act<NT1, 0, 0, MINW, HGNN_ACT_GELU, HGNN_ACT_GELU>(a, s);
-        case HGNN_ACT_TANH: return launch_mlp_act<NT1, 0, 0, MINW, HGNN_ACT_TANH, HGNN_ACT_TANH>(a, s);
+        case HGNN_ACT_GELU: return launch_mlp_act<NT1, 0, 0, MINW, HGNN_ACT_GELU, HGNN_ACT_GELU, false, 4, PARTIAL>(a, s);
+        case HGNN_ACT_TANH: return launch_mlp_act<NT1, 0, 0, MINW, HGNN_ACT_TANH, HGNN_ACT_TANH, false, 4, PARTIAL>(a, s);
     }
-    return launch_mlp_act<NT1, 0, 0, MINW, -1, -1>(a, s);
+    return launch_mlp_act<NT1, 0, 0, MINW, -1, -1, false, 4, PARTIAL>(a, s);
 }
 
 // heads: K -> H -> H -> w with a PLAIN last layer of w <= 32 real outputs (padded to 32 rows): the width-1
@@ -568,8 +572,15 @@ extern "C" int hgnn_mlp_supported(const hgnn_mlp_desc* d) {
     const int o = d->width[n];
     if (n == 1) {
         // a single Linear -> LayerNorm -> act (+ skip) layer, 512 or 1024 wide: the building block of the fp32
-        // MLPs at latent 512 (hidden 1024), which do not fit one launch
-        if (d->ln_w[0] == nullptr || d->ln_b[0] == nullptr || d->w_last_rows != 0 || d->save_pre[0] != nullptr) return 0;
+        // MLPs at latent 512 (hidden 1024), which do not fit one launch; save_pre[0] dumps its pre-LayerNorm rows (the
+        // first Linear of the encoders under autograd)
+        if (d->ln_w[0] == nullptr || d->ln_b[0] == nullptr) return 0;
+        if (d->w_last_rows != 0) {
+            // narrower than its zero-padded storage of P = 512 rows (W, b, ln_w, ln_b): P - 16 < o < P, o % 4 == 0 (the
+            // 504-wide last layer of the supernode encoder at latent 512); inference only
+            const int P = d->w_last_rows;
+            return (P == 512 && o > P - 16 && o < P && (o & 3) == 0 && d->skip == nullptr && d->save_pre[0] == nullptr) ? 1 : 0;
+        }
         return (o == 512 || o == 1024) ? 1 : 0;
     }
     if (n == 3 && d->width[2] != h) return 0;
@@ -671,6 +682,7 @@ extern "C" int hgnn_mlp_forward_f32(const hgnn_mlp_desc* d, float* out, hgnn_str
     }
     const int o = d->width[d->n_layers];
     if (d->n_layers == 1) {
+        if (d->w_last_rows == 512 && o < 512) return launch_single<32, 2, true>(a, stream);
         switch (o) {
             case 512: return launch_single<32, 2>(a, stream);
             case 1024: return launch_single<64, 1>(a, stream);

@@ -36,7 +36,11 @@ _enabled = True
 # segment-reduced dz it is faster (L=256, M=2M cell step: 58 vs 122 ms checkpointed, 45 vs 92 ms
 # without checkpointing) and is the default when autograd records.
 _train_enabled = True
-stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0}
+# library_calls: concat_mlp evaluated a Sequential with library GEMMs (no fused route); library_dgrad_calls: a data
+# gradient of the bf16 training backward went through a library GEMM; bwd_layer_calls: launches of the fused backward
+# layer; hybrid_train_calls: encoders under autograd on the fp32 first layer + bf16 tail (mlp.concat_mlp)
+stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0, "library_calls": 0, "library_dgrad_calls": 0,
+         "bwd_layer_calls": 0, "hybrid_train_calls": 0}
 
 # Dispatch switches.  The module-level ``_name`` variables below are the PROCESS DEFAULTS (what the ``set_*`` functions
 # and the HGNN_* environment variables change).  ``options(...)`` overrides any of them for the current context only --
@@ -45,7 +49,7 @@ stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0}
 _ctx_options = contextvars.ContextVar("hgnn_fused_options", default=None)
 _ctx_training_forward = contextvars.ContextVar("hgnn_fused_training_forward", default=0)
 _OPTION_NAMES = ("enabled", "train_enabled", "preproject", "preproject_bf16", "fp32_split3", "fp32_split3_train",
-                 "bf16_split", "train_bf16_enabled")
+                 "bf16_split", "train_bf16_enabled", "strict")
 
 
 def _opt(name: str):
@@ -58,7 +62,8 @@ def _opt(name: str):
 @contextlib.contextmanager
 def options(**overrides):
     """Context-local dispatch overrides: ``enabled``, ``train_enabled``, ``preproject``, ``preproject_bf16``,
-    ``fp32_split3``, ``fp32_split3_train``, ``bf16_split``, ``train_bf16_enabled``.
+    ``fp32_split3``, ``fp32_split3_train``, ``bf16_split``, ``train_bf16_enabled``, ``strict``.
+    ``strict``: ``concat_mlp`` raises instead of evaluating a Sequential on the library path (see ``set_strict``).
     Nested contexts stack; nothing outside the ``with`` block (or in another thread) sees the change.
     NOTE for training: autograd runs the backward (and the recompute of reentrant checkpoints) on its own worker
     thread, which does NOT inherit this context -- switches that must hold during ``backward()`` (``fp32_split3_train``,
@@ -82,6 +87,19 @@ def set_enabled(flag: bool, train: bool = None):
     global _enabled, _train_enabled
     _enabled = bool(flag)
     _train_enabled = bool(train) if train is not None else bool(flag)
+
+
+_strict = False
+
+
+def set_strict(flag: bool) -> None:
+    """Process default of the ``strict`` option: ``mlp.concat_mlp`` raises ``RuntimeError`` (naming the layer widths
+    and dtypes) where it would otherwise leave the fused kernels and evaluate the Sequential with library GEMMs
+    (counted in ``stats["library_calls"]``).  ``options(strict=True)`` is context-local and therefore covers the
+    forwards of the calling thread; a backward -- and the recompute of a reentrant checkpoint -- runs on autograd's
+    own thread, which only the process default set here reaches."""
+    global _strict
+    _strict = bool(flag)
 
 
 def _parse(net: nn.Sequential):
@@ -341,6 +359,12 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
                     return None
                 W, b, lnw, lnb = (_pad_rows(p, P) for p in (W, b, lnw, lnb))
                 d.w_last_rows = P
+            elif n == 1 and ln is not None and 496 < o_l < 512 and o_l % 4 == 0:
+                # the narrow last layer of a chain (supernode encoder at latent 512, 504 outputs): one single-layer
+                # launch on parameters zero-padded to 512 rows, statistics and stores over the real width
+                if not dry:
+                    W, b, lnw, lnb = (_pad_rows(p, 512) for p in (W, b, lnw, lnb))
+                d.w_last_rows = 512
         keep += [W, b, lnw, lnb]
         d.W[l], d.b[l] = W.data_ptr(), b.data_ptr()
         if ln is not None:
@@ -676,7 +700,12 @@ def _route(net, segments, skip, *, train: bool, allow_chain: bool = True) -> Opt
         if len(layers) < 2 or any(ln is None for _, ln, _ in layers[:-1]):
             return False
         fused_layers = layers if layers[-1][1] is not None else layers[:-1]
-        if any(lin.out_features not in (512, 1024) or lin.in_features % 16 for lin, _, _ in fused_layers[1:]) \
+        # fp32: the chain may END in a LayerNorm'ed layer narrower than its 512-row storage (504: supernode encoder)
+        o_last = layers[-1][0].out_features
+        narrow = not bf16 and layers[-1][1] is not None and skip is None and 496 < o_last < 512 and o_last % 4 == 0
+        wide = fused_layers[1:-1] if narrow else fused_layers[1:]
+        if any(lin.out_features not in (512, 1024) or lin.in_features % 16 for lin, _, _ in wide) \
+                or (narrow and fused_layers[-1][0].in_features % 16) \
                 or fused_layers[0][0].out_features not in (512, 1024):
             return False
         if bf16 and not _wants_split(None, segments, fused_layers[:1]):
@@ -1065,7 +1094,24 @@ def set_train_bf16(flag: bool) -> None:
     _train_bf16_enabled = bool(flag)
 
 
+# the fused backward layer at N = 1024 (hidden width of latent 512): default decided by tools/bench_bwd_layer.py --wide
+# (DESIGN.md section 3); off = the unfused route (library GEMM + two HIP row passes).  Measured on 32-row tiles (the
+# geometry without scratch): 8.9 against 8.0 ms at (512, 1024), 11.6 against 9.4 ms at (1024, 1024), M = 2M -- slower,
+# so it ships OFF (profiles/bwd_layer_n1024.json)
+_bwd_layer_wide = os.environ.get("HGNN_BWD_LAYER_WIDE", "0") == "1"
+
+
+def set_bwd_layer_wide(flag: bool) -> None:
+    """process default (the backward runs on autograd's thread, which no ``options`` context reaches): the bf16 training
+    backward takes ``hgnn_mlp_backward_layer_bf16`` at N = 1024 too (HGNN_BWD_LAYER_WIDE=1)"""
+    global _bwd_layer_wide
+    _bwd_layer_wide = bool(flag)
+
+
 def _bwd_layer_supported(K: int, N: int) -> bool:
+    """the bf16 training backward routes this boundary to the fused backward layer"""
+    if int(N) == 1024 and not _bwd_layer_wide:
+        return False
     return bool(_lib.load().hgnn_mlp_backward_layer_supported_bf16(int(K), int(N)))
 
 
@@ -1088,6 +1134,7 @@ def _bwd_layer(dz, W, z_prev, gamma, beta, act, eps, skip=None, want_a=False):
             _lib.ptr(dz.contiguous()), M, K, N, _lib.ptr(wt), _lib.ptr(z_prev), _lib.ptr(gm), _lib.ptr(bt), int(act),
             float(eps), _lib.ptr(sk), _lib.ptr(out), _lib.ptr(a_prev), _lib.ptr(partials),
             _lib.current_stream(dev)), "hgnn_mlp_backward_layer_bf16")
+    stats["bwd_layer_calls"] += 1
     if not ln:
         return (out,)
     sums = partials.sum(dim=0)
@@ -1198,6 +1245,7 @@ class _FusedMLPTrainBf16(torch.autograd.Function):
                 grads_params[4 * l] = wgrad_bf16(dz, a_prev, colsum=colsum).to(pdt[l])
                 del a_prev
                 da = dz @ W[l].detach().to(bf)                            # data gradient: bf16 library GEMM
+                stats["library_dgrad_calls"] += 1
                 dz_prev, dlw, dlb, dbias_prev = _ln_act_backward(zs[l - 1], da, lnw[l - 1], lnb[l - 1],
                                                                  ctx.acts[l - 1], ctx.eps)
                 del da
@@ -1238,8 +1286,10 @@ class _FusedMLPTrainBf16(torch.autograd.Function):
                                                        skip=g if folded else None)[0]
                     elif folded:
                         grads_tables[s_i] = torch.addmm(g, dz, W_s)
+                        stats["library_dgrad_calls"] += 1
                     else:
                         grads_tables[s_i] = dz @ W_s
+                        stats["library_dgrad_calls"] += 1
             col += w_s
         if need_bias:
             grads_params[1] = dz.float().sum(dim=0).to(pdt[0])

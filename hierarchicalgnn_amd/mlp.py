@@ -9,7 +9,9 @@ row-gather kernel (backward: atomics-free segmented reduce).  The dense layers
 are evaluated by the fused fp32-MFMA kernel when the shape is supported
 (``fused.py``: forward-only when autograd is off, a differentiable variant with a
 hand-written backward when it records), otherwise by the library GEMM path (rocBLAS
-through ATen) -- all on the GPU; none is a CPU fallback.
+through ATen) -- all on the GPU; none is a CPU fallback.  Every call that takes the library
+path is counted in ``fused.stats["library_calls"]``; with the ``strict`` option
+(``fused.options(strict=True)`` / ``fused.set_strict``) it raises instead.
 """
 from __future__ import annotations
 
@@ -54,6 +56,41 @@ def concat_mlp(net: nn.Sequential, segments: Sequence[Segment], skip: Optional[t
         or fused._route(net, segments, skip, train=True)
     if r is not None:
         return fused._run(r, segments, skip)
+    if bf16_tail and skip is None and len(net) > 3 and torch.is_grad_enabled() and fused._opt("enabled") \
+            and all(t.dtype == torch.float32 and t.is_cuda for t, _ in segments):
+        # the same hybrid chain under autograd (encoders at latent 512, whose 1024-wide hidden layers have no fp32
+        # training kernel): the first Linear as ONE differentiable fp32 layer (small-K, dump at its real width), the
+        # cast, the wide tail on the differentiable bf16 feature-split kernel -- only when both routes exist
+        first, rest = nn.Sequential(*list(net)[:3]), nn.Sequential(*list(net)[3:])
+        r_first = fused._route(first, segments, None, train=True)
+        probe = [(torch.empty((0, net[0].out_features), dtype=torch.bfloat16, device=segments[0][0].device), None)]
+        r_rest = None if r_first is None else fused._route(rest, probe, None, train=True)
+        if r_rest is not None:
+            fused.stats["hybrid_train_calls"] += 1
+            y = fused._run(r_first, segments, None)
+            return fused._run(r_rest, [(y.to(torch.bfloat16), None)], None)
+    if not torch.is_grad_enabled() and fused._opt("enabled") and not bf16_tail \
+            and fused._ctx_training_forward.get() == 0 \
+            and all(t.dtype == torch.bfloat16 and t.is_cuda for t, _ in segments) \
+            and (skip is None or skip.dtype == torch.bfloat16) and next(net.parameters()).dtype == torch.float32:
+        # bf16 rows and a net no bf16 kernel accepts (the supernode encoder, latent - emb_dim outputs: the bf16 kernels
+        # have no real-width LayerNorm): the fp32 kernels on the rows cast up, the result cast down -- a few thousand
+        # pooled rows, the casts are noise.  Not in the no-grad pass of a checkpointed training step: its recompute
+        # under autograd takes the library path, and the two must agree
+        seg32 = [(t.float(), i) for t, i in segments]
+        skip32 = None if skip is None else skip.float()
+        r = fused._route(net, seg32, skip32, train=False)
+        if r is not None:
+            return fused._run(r, seg32, skip32).to(torch.bfloat16)
+    if fused._opt("strict"):
+        widths = [m.in_features for m in net if isinstance(m, nn.Linear)][:1] + \
+            [m.out_features for m in net if isinstance(m, nn.Linear)]
+        raise RuntimeError(
+            "concat_mlp (strict): no fused kernel for layer widths " + " -> ".join(str(w) for w in widths) +
+            f", rows {[str(t.dtype) for t, _ in segments]} of widths {[int(t.shape[1]) for t, _ in segments]}"
+            f", parameters {next(net.parameters()).dtype}, skip={skip is not None}, bf16_tail={bf16_tail}"
+            f", autograd {'on' if torch.is_grad_enabled() else 'off'}: this call would run on library GEMMs")
+    fused.stats["library_calls"] += 1
     parts: List[torch.Tensor] = []
     for table, index in segments:
         parts.append(table if index is None else gather_rows(table, index))

@@ -381,7 +381,10 @@ typedef struct hgnn_mlp_desc {
  *       H in {64, 128, 256, 512}, no skip; out is float[M, w];
  *   single layers: n_layers = 1, K -> o with o in {512, 1024}, LayerNorm + activation (+ skip): the pieces of an
  *       fp32 MLP at latent 512 (its 1024-wide hidden layer is 256 accumulators per lane: one launch per layer, the
- *       hidden rows make one trip through HBM);
+ *       hidden rows make one trip through HBM); save_pre[0] dumps the pre-LayerNorm rows (training forward of the
+ *       encoders' first Linear).  Narrow single layer (inference): 496 < o < 512, o % 4 == 0, W / b / ln_w / ln_b
+ *       zero padded to 512 rows (w_last_rows = 512), no skip, no save_pre: LayerNorm over the o real features,
+ *       out is float[M, o] (the last layer of the supernode encoder at latent 512);
  *   narrow encoders: K -> 2P -> 2P -> o with P in {32, 64, 128, 256}, P-16 < o < P, o % 4 == 0, the last
  *       layer's W / b / ln_w / ln_b zero padded to P rows (w_last_rows = P), no skip, no save_pre;
  *       LayerNorm over the o real features; out is float[M, o]. */
@@ -521,8 +524,11 @@ int hgnn_wgrad_f32_split3(const float* A, int64_t lda, const float* B, int64_t l
  *   z_prev == NULL ("input form"):      out = dz . W (+ skip): gradient of a direct input segment of the first
  *       layer, the skip connection's gradient (skip [M,N] bf16, may be NULL) added in the epilogue.
  * Wt_frag: W^T (the [N][K] matrix) in the MFMA A-fragment order of hgnn_mlp_forward_bf16_split.
- * K a multiple of 128, N in {128, 256, 512}; all rows bf16, fp32 accumulation and LayerNorm arithmetic; deterministic. */
+ * K a multiple of 128, N in {128, 256, 512, 1024}; all rows bf16, fp32 accumulation and LayerNorm arithmetic;
+ * deterministic.  A workgroup walks row tiles of 64 rows (N <= 512) or HGNN_MLP_BWD_TILE_ROWS_N1024 rows (N = 1024,
+ * the hidden width of latent 512: 8 waves, 8 feature tiles each). */
 #define HGNN_MLP_BWD_BLOCKS 512
+#define HGNN_MLP_BWD_TILE_ROWS_N1024 32
 int hgnn_mlp_backward_layer_supported_bf16(int32_t K, int32_t N);
 int hgnn_mlp_backward_layer_bf16(const void* dz, int64_t M, int32_t K, int32_t N, const void* Wt_frag,
                                  const void* z_prev, const float* ln_w, const float* ln_b, int32_t act, float eps,

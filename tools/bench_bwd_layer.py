@@ -1,6 +1,12 @@
 #!/usr/bin/env python3
 """Fused backward layer (hgnn_mlp_backward_layer_bf16) vs the unfused pieces it replaces (bf16 library GEMM + HIP
-LayerNorm/activation row passes), M = 2M rows.  Usage: bench_bwd_layer.py"""
+LayerNorm/activation row passes), M = 2M rows.  Usage: bench_bwd_layer.py [--wide [OUT.json]]
+
+--wide: the N = 1024 instance (hidden width of latent 512) on GELU -- LayerNorm form (K, N) in {(512, 1024),
+(1024, 1024)} at M = 2,000,000 and M = 120,000, input form (1024, 512) at M = 2,000,000 -- fused against unfused in
+the same process, the two ALTERNATING call by call, median and max - min of 10 timed calls each after 3 warm-up calls.
+The rule for the default of fused.set_bwd_layer_wide: on only if, at both M for both LayerNorm
+shapes, the median gain exceeds three times the unfused route's own max - min spread."""
 import json
 import os
 import sys
@@ -25,6 +31,72 @@ def t(fn, reps=8):
     ts.sort()
     return ts[len(ts) // 2]
 
+
+def ab(unfused, fused_fn, reps=10, warm=3):
+    """alternate the two routes call by call; (median, max - min) of each"""
+    for _ in range(warm):
+        unfused()
+        fused_fn()
+    torch.cuda.synchronize()
+    ts = {"unfused": [], "fused": []}
+    for _ in range(reps):
+        for name, fn in (("unfused", unfused), ("fused", fused_fn)):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            fn()
+            e.record()
+            torch.cuda.synchronize()
+            ts[name].append(s.elapsed_time(e))
+    r = {"calls": reps}
+    for name, v in ts.items():
+        v.sort()
+        r[name + "_ms"] = round(v[len(v) // 2], 4)
+        r[name + "_spread_ms"] = round(v[-1] - v[0], 4)
+    r["gain_ms"] = round(r["unfused_ms"] - r["fused_ms"], 4)
+    r["passes_rule"] = bool(r["gain_ms"] > 3 * r["unfused_spread_ms"])
+    return r
+
+
+def wide():
+    res = {"kernel": "k_mlp_bwd_layer<8, EPI, 0, 1, 8, 2, true>  (N = 1024: 8 waves x 32-row tiles)", "act": "GELU",
+           "tile_rows": _lib.MLP_BWD_TILE_ROWS_N1024, "cases": {}}
+    fused.set_bwd_layer_wide(True)
+    for K, N in ((512, 1024), (1024, 1024)):
+        for M in (2_000_000, 120_000):
+            dz = torch.randn(M, K, device="cuda").bfloat16()
+            W = torch.randn(K, N, device="cuda") / K ** 0.5
+            z = torch.randn(M, N, device="cuda").bfloat16()
+            gm, bt = torch.ones(N, device="cuda"), torch.zeros(N, device="cuda")
+            Wb = W.bfloat16()
+
+            def unfused():
+                da = dz @ Wb
+                return fused._ln_act_backward(z, da, gm, bt, 1, 1e-5), fused._ln_act_forward(z, gm, bt, 1, 1e-5)
+
+            res["cases"][f"ln_form_K{K}_N{N}_M{M}"] = ab(
+                unfused, lambda: fused._bwd_layer(dz, W, z, gm, bt, 1, 1e-5, want_a=True))
+            del dz, z
+            torch.cuda.empty_cache()
+    M, K, N = 2_000_000, 1024, 512
+    dz = torch.randn(M, K, device="cuda").bfloat16()
+    W = torch.randn(K, N, device="cuda") / K ** 0.5
+    skip = torch.randn(M, N, device="cuda").bfloat16()
+    Wb = W.bfloat16()
+    res["cases"][f"input_form_K{K}_N{N}_M{M}"] = ab(
+        lambda: torch.addmm(skip, dz, Wb), lambda: fused._bwd_layer(dz, W, None, None, None, 0, 1e-5, skip=skip))
+    res["default_on_by_rule"] = all(c["passes_rule"] for k, c in res["cases"].items() if k.startswith("ln_form"))
+    text = json.dumps(res, indent=1)
+    args = [a for a in sys.argv[1:] if a != "--wide"]
+    if args:
+        os.makedirs(os.path.dirname(os.path.abspath(args[0])), exist_ok=True)
+        with open(args[0], "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
+if "--wide" in sys.argv[1:]:
+    wide()
+    sys.exit(0)
 
 M = 2_000_000
 out = {}

@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Secondary figures at the BASELINE shape: (a) one InteractionGNNCell forward+backward under
 reentrant checkpointing (the way the reference trains), (b) one HierarchicalGNNCell inference
-forward with the synthetic hierarchy (S=10k, B=600k, Q~200k).  Usage: bench_train_step.py [L]"""
+forward with the synthetic hierarchy (S=10k, B=600k, Q~200k).  Usage: bench_train_step.py [L]
+
+bench_train_step.py 512 wide_ab [OUT.json]: instead, one EC-IN training step at latent 512 with bf16 rows (BASELINE
+config 4's dtype; forward + BCE + backward, reentrant checkpointing) with the N = 1024 fused backward layer off and on
+(fused.set_bwd_layer_wide), the two alternating step by step in one process: median and max - min of 5 steps each."""
 import json
 import os
 import sys
@@ -12,6 +16,59 @@ import hierarchicalgnn_amd as H
 from hierarchicalgnn_amd import fused, synth
 
 L = int(sys.argv[1]) if len(sys.argv) > 1 else 256
+
+
+def wide_ab():
+    from hierarchicalgnn_amd.models import EC_InteractionGNN
+    torch.manual_seed(1236)
+    hp = dict(spatial_channels=3, latent=L, hidden=2 * L, n_interaction_graph_iters=14, nb_node_layer=3,
+              nb_edge_layer=2, output_layers=3, hidden_output_activation="GELU", hidden_activation="GELU",
+              layernorm=True, share_weight=False, checkpointing=True, feature_dtype="bf16")
+    model = EC_InteractionGNN(hp).cuda().train()
+    x, ei = synth.trackml_event()
+    x, ei = x.cuda(), ei.cuda()
+    target = (torch.rand(ei.shape[1], device="cuda") < 0.3).float()
+
+    def step():
+        loss = torch.nn.functional.binary_cross_entropy(model(x, ei), target)
+        loss.backward()
+        model.zero_grad(set_to_none=True)
+
+    res = {"model": "EC-IN", "latent": L, "feature_dtype": "bf16", "cells": 14, "checkpointing": True,
+           "N": int(x.shape[0]), "E": int(ei.shape[1])}
+    ts = {False: [], True: []}
+    for flag in (False, True):
+        fused.set_bwd_layer_wide(flag)
+        step()
+    torch.cuda.synchronize()
+    for _ in range(5):
+        for flag in (False, True):
+            fused.set_bwd_layer_wide(flag)
+            c0 = {k: fused.stats[k] for k in ("bwd_layer_calls", "library_dgrad_calls", "library_calls", "hybrid_train_calls")}
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            step()
+            b.record()
+            torch.cuda.synchronize()
+            ts[flag].append(a.elapsed_time(b))
+            res[f"counters_wide_{'on' if flag else 'off'}"] = {k: fused.stats[k] - v for k, v in c0.items()}
+    for flag, v in ts.items():
+        v.sort()
+        name = "on" if flag else "off"
+        res[f"train_step_wide_{name}_ms"] = round(v[len(v) // 2], 2)
+        res[f"train_step_wide_{name}_spread_ms"] = round(v[-1] - v[0], 2)
+    text = json.dumps(res, indent=1)
+    out = [a for a in sys.argv[3:]]
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out[0])), exist_ok=True)
+        with open(out[0], "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
+if "wide_ab" in sys.argv[2:3]:
+    wide_ab()
+    sys.exit(0)
 torch.manual_seed(0)
 x, ei = synth.trackml_event()
 graph = synth.directed(ei).cuda()
