@@ -34,6 +34,7 @@
 //     zero-padded parameters; LayerNorm statistics masked to the real features, dumps / skip / stores at the real
 //     row widths.  PAD is false for every kernel of the native grid, whose device code does not depend on it.
 #include "mlp_common.h"
+#include "mlp_desc.h"
 #include "options.h"
 
 namespace hgnn {
@@ -546,28 +547,15 @@ static bool is_partial(const hgnn_mlp_desc* d) {
 
 using namespace hgnn;
 
+// 16-column chunks or small-K, padded storage; LayerNorm-less last layers (heads) and M are checked below / in the forward
+static const MlpDescRules kRulesF32 = {/*seg_multiple*/ 16, /*padded_storage*/ true, /*layers*/ 1, 3,
+                                       /*ln_everywhere*/ false, /*save_pre*/ true, /*max_pre*/ 2, /*m_int32*/ false};
+static const MlpDescRules kRulesF32Padded = {/*seg_multiple*/ 16, /*padded_storage*/ true, /*layers*/ 2, 3,
+                                             /*ln_everywhere*/ false, /*save_pre*/ true, /*max_pre*/ 2, /*m_int32*/ false};
+
 extern "C" int hgnn_mlp_supported(const hgnn_mlp_desc* d) {
-    if (d == nullptr) return 0;
-    if (d->n_seg < 1 || d->n_seg > 3 || d->n_layers < 1 || d->n_layers > 3) return 0;
-    int k = 0;
-    bool aligned16 = true;
-    for (int s = 0; s < d->n_seg; ++s) {
-        if (d->seg_width[s] <= 0) return 0;
-        aligned16 = aligned16 && d->seg_width[s] % 16 == 0;
-        k += d->seg_width[s];
-    }
-    if (k != d->width[0]) return 0;
-    if (!aligned16) {  // small-K mode: one zero-padded 16-column chunk
-        if (k > 16 || d->w0_cols != 16) return 0;
-    } else if (d->w0_cols != 0 && d->w0_cols != k) {
-        return 0;
-    }
+    if (!mlp_desc_shape_ok(d, kRulesF32)) return 0;
     const int n = d->n_layers;
-    for (int l = 0; l < n; ++l)
-        if (d->W[l] == nullptr || d->b[l] == nullptr) return 0;
-    if (d->n_pre < 0 || d->n_pre > 2) return 0;
-    for (int s = 0; s < d->n_pre; ++s)
-        if (d->pre_table[s] == nullptr || d->pre_index[s] == nullptr) return 0;
     const int h = d->width[1];
     const int o = d->width[n];
     if (n == 1) {
@@ -583,7 +571,6 @@ extern "C" int hgnn_mlp_supported(const hgnn_mlp_desc* d) {
         }
         return (o == 512 || o == 1024) ? 1 : 0;
     }
-    if (n == 3 && d->width[2] != h) return 0;
     if (is_head(d)) {
         // K -> H -> H -> w (w <= 32): LayerNorm on the hidden layers only, plain last layer stored as 32 rows
         if (o < 1 || o > 32 || d->w_last_rows != 32 || d->act[2] != HGNN_ACT_NONE) return 0;
@@ -615,55 +602,20 @@ extern "C" int hgnn_mlp_forward_f32(const hgnn_mlp_desc* d, float* out, hgnn_str
         return HGNN_ERR_UNSUPPORTED;
     }
     if (d->M == 0) return HGNN_OK;
-    HGNN_REQUIRE(d->M > 0 && d->M < ((int64_t)1 << 31) * 64, "hgnn_mlp_forward_f32: bad M");
+    static const char fn[] = "hgnn_mlp_forward_f32";
+    HGNN_REQUIRE(d->M > 0 && d->M < ((int64_t)1 << 31) * 64, "%s: bad M", fn);   // the grid (M / 64 workgroups) is 32 bits
     MlpArgs a;
-    for (int s = 0; s < 3; ++s) {
-        a.seg_table[s] = s < d->n_seg ? d->seg_table[s] : nullptr;
-        a.seg_index[s] = s < d->n_seg ? d->seg_index[s] : nullptr;
-        a.seg_width[s] = s < d->n_seg ? d->seg_width[s] : 0;
-        if (s < d->n_seg) {
-            HGNN_REQUIRE(a.seg_table[s] != nullptr && (uintptr_t)a.seg_table[s] % 16 == 0,
-                         "hgnn_mlp_forward_f32: segment table %d is NULL or not 16-byte aligned", s);
-        }
-    }
-    a.n_seg = d->n_seg;
+    HGNN_TRY(unpack_segments(a, d, fn));
     a.K1_real = d->width[0];
-    a.K1 = d->w0_cols != 0 ? d->w0_cols : d->width[0];
     a.n_out_real = d->width[d->n_layers];
-    for (int l = 0; l < 3; ++l) {
-        const bool on = l < d->n_layers;
-        a.W[l] = on ? d->W[l] : nullptr;
-        a.b[l] = on ? d->b[l] : nullptr;
-        a.lnw[l] = on ? d->ln_w[l] : nullptr;
-        a.lnb[l] = on ? d->ln_b[l] : nullptr;
-        a.act[l] = on ? d->act[l] : 0;
-        if (on) {
-            HGNN_REQUIRE((uintptr_t)a.W[l] % 16 == 0 && (uintptr_t)a.b[l] % 16 == 0 &&
-                             (uintptr_t)a.lnw[l] % 16 == 0 && (uintptr_t)a.lnb[l] % 16 == 0,
-                         "hgnn_mlp_forward_f32: layer %d parameters must be 16-byte aligned", l);
-        }
-        if (on && a.lnw[l] == nullptr) a.lnw[l] = a.lnb[l] = a.b[l];  // never dereferenced (plain layer)
-    }
+    for (int l = 0; l < 3; ++l) HGNN_TRY(unpack_layer(a, d, l, fn));
     a.ablate = g_opt_mlp_ablate;
-    for (int l = 0; l < 3; ++l) {
-        a.save_pre[l] = l < d->n_layers ? d->save_pre[l] : nullptr;
-        HGNN_REQUIRE((uintptr_t)a.save_pre[l] % 16 == 0, "hgnn_mlp_forward_f32: save_pre[%d] must be 16-byte aligned", l);
-    }
+    for (int l = 0; l < 3; ++l) HGNN_TRY(unpack_save_pre(a, d, l, fn));
     // heads: the two LayerNorm'ed hidden layers can dump (training forward of the score heads); the plain last layer's
     // "pre-LayerNorm output" is the result itself
-    HGNN_REQUIRE(!(is_head(d) && d->save_pre[2]), "hgnn_mlp_forward_f32: save_pre[2] is not available for heads");
-    a.eps = d->ln_eps;
-    a.skip = d->skip;
-    a.out = out;
-    a.n_pre = d->n_pre;
-    for (int s = 0; s < 2; ++s) {
-        a.pre_table[s] = s < d->n_pre ? d->pre_table[s] : nullptr;
-        a.pre_index[s] = s < d->n_pre ? d->pre_index[s] : nullptr;
-        HGNN_REQUIRE((uintptr_t)a.pre_table[s] % 16 == 0, "hgnn_mlp_forward_f32: pre_table[%d] must be 16-byte aligned", s);
-    }
-    a.M = d->M;
-    HGNN_REQUIRE((uintptr_t)out % 16 == 0 && (uintptr_t)a.skip % 16 == 0,
-                 "hgnn_mlp_forward_f32: out/skip must be 16-byte aligned");
+    HGNN_REQUIRE(!(is_head(d) && d->save_pre[2]), "%s: save_pre[2] is not available for heads", fn);
+    HGNN_TRY(unpack_pre(a, d, fn));
+    HGNN_TRY(unpack_out_skip(a, d, out, fn));
     if (is_head(d)) {
         switch (d->width[1]) {
             case 64: return launch_head<4, 2>(a, stream);
@@ -708,30 +660,10 @@ extern "C" int hgnn_mlp_forward_f32(const hgnn_mlp_desc* d, float* out, hgnn_str
 }
 
 extern "C" int hgnn_mlp_supported_f32_padded(const hgnn_mlp_desc* d) {
-    if (d == nullptr) return 0;
-    if (d->n_seg < 1 || d->n_seg > 3 || d->n_layers < 2 || d->n_layers > 3) return 0;
-    int k = 0;
-    bool aligned16 = true;
-    for (int s = 0; s < d->n_seg; ++s) {
-        if (d->seg_width[s] <= 0) return 0;
-        aligned16 = aligned16 && d->seg_width[s] % 16 == 0;
-        k += d->seg_width[s];
-    }
-    if (k != d->width[0]) return 0;
-    if (!aligned16) {  // small-K mode: one zero-padded 16-column chunk
-        if (k > 16 || d->w0_cols != 16) return 0;
-    } else if (d->w0_cols != 0 && d->w0_cols != k) {
-        return 0;
-    }
+    if (!mlp_desc_shape_ok(d, kRulesF32Padded)) return 0;
     const int n = d->n_layers;
-    for (int l = 0; l < n; ++l)
-        if (d->W[l] == nullptr || d->b[l] == nullptr) return 0;
-    if (d->n_pre < 0 || d->n_pre > 2) return 0;
-    for (int s = 0; s < d->n_pre; ++s)
-        if (d->pre_table[s] == nullptr || d->pre_index[s] == nullptr) return 0;
     const int h = d->width[1];
     const int o = d->width[n];
-    if (n == 3 && d->width[2] != h) return 0;
     const int P = pad_grid(h);
     if (P == 0) return 0;
     if (d->ln_w[0] == nullptr || d->ln_b[0] == nullptr || d->ln_w[1] == nullptr || d->ln_b[1] == nullptr) return 0;
@@ -758,54 +690,21 @@ extern "C" int hgnn_mlp_forward_f32_padded(const hgnn_mlp_desc* d, float* out, h
         return HGNN_ERR_UNSUPPORTED;
     }
     if (d->M == 0) return HGNN_OK;
-    HGNN_REQUIRE(d->M > 0 && d->M < ((int64_t)1 << 31) * 64, "hgnn_mlp_forward_f32_padded: bad M");
+    static const char fn[] = "hgnn_mlp_forward_f32_padded";
+    HGNN_REQUIRE(d->M > 0 && d->M < ((int64_t)1 << 31) * 64, "%s: bad M", fn);
     const int n = d->n_layers;
     MlpArgs a;
-    for (int s = 0; s < 3; ++s) {
-        a.seg_table[s] = s < d->n_seg ? d->seg_table[s] : nullptr;
-        a.seg_index[s] = s < d->n_seg ? d->seg_index[s] : nullptr;
-        a.seg_width[s] = s < d->n_seg ? d->seg_width[s] : 0;
-        if (s < d->n_seg) {
-            HGNN_REQUIRE(a.seg_table[s] != nullptr && (uintptr_t)a.seg_table[s] % 16 == 0,
-                         "hgnn_mlp_forward_f32_padded: segment table %d is NULL or not 16-byte aligned", s);
-        }
-    }
-    a.n_seg = d->n_seg;
+    HGNN_TRY(unpack_segments(a, d, fn));
     a.K1_real = d->width[0];
-    a.K1 = d->w0_cols != 0 ? d->w0_cols : d->width[0];
     a.n_out_real = d->width[n];
-    for (int l = 0; l < 3; ++l) {
-        const bool on = l < n;
-        a.W[l] = on ? d->W[l] : nullptr;
-        a.b[l] = on ? d->b[l] : nullptr;
-        a.lnw[l] = on ? d->ln_w[l] : nullptr;
-        a.lnb[l] = on ? d->ln_b[l] : nullptr;
-        a.act[l] = on ? d->act[l] : 0;
-        a.real[l] = on ? d->width[l + 1] : 0;
-        if (on) {
-            HGNN_REQUIRE((uintptr_t)a.W[l] % 16 == 0 && (uintptr_t)a.b[l] % 16 == 0 &&
-                             (uintptr_t)a.lnw[l] % 16 == 0 && (uintptr_t)a.lnb[l] % 16 == 0,
-                         "hgnn_mlp_forward_f32_padded: layer %d parameters must be 16-byte aligned", l);
-        }
-        if (on && a.lnw[l] == nullptr) a.lnw[l] = a.lnb[l] = a.b[l];  // never dereferenced (plain layer)
-        a.save_pre[l] = on ? d->save_pre[l] : nullptr;
-        HGNN_REQUIRE((uintptr_t)a.save_pre[l] % 16 == 0,
-                     "hgnn_mlp_forward_f32_padded: save_pre[%d] must be 16-byte aligned", l);
+    for (int l = 0; l < 3; ++l) {   // this entry has always checked each layer's dump right after its parameters
+        HGNN_TRY(unpack_layer(a, d, l, fn));
+        a.real[l] = l < n ? d->width[l + 1] : 0;
+        HGNN_TRY(unpack_save_pre(a, d, l, fn));
     }
     a.ablate = g_opt_mlp_ablate;
-    a.eps = d->ln_eps;
-    a.skip = d->skip;
-    a.out = out;
-    a.n_pre = d->n_pre;
-    for (int s = 0; s < 2; ++s) {
-        a.pre_table[s] = s < d->n_pre ? d->pre_table[s] : nullptr;
-        a.pre_index[s] = s < d->n_pre ? d->pre_index[s] : nullptr;
-        HGNN_REQUIRE((uintptr_t)a.pre_table[s] % 16 == 0,
-                     "hgnn_mlp_forward_f32_padded: pre_table[%d] must be 16-byte aligned", s);
-    }
-    a.M = d->M;
-    HGNN_REQUIRE((uintptr_t)out % 16 == 0 && (uintptr_t)a.skip % 16 == 0,
-                 "hgnn_mlp_forward_f32_padded: out/skip must be 16-byte aligned");
+    HGNN_TRY(unpack_pre(a, d, fn));
+    HGNN_TRY(unpack_out_skip(a, d, out, fn));
     const int P = pad_grid(d->width[1]);
     if (is_head(d)) {
         switch (P) {

@@ -15,6 +15,7 @@
 //   * bf16 MFMA does NOT share the fp32 vector ALUs, so LayerNorm/GELU epilogues of one wave overlap
 //     the co-resident waves' MFMAs.
 #include "mlp_common.h"
+#include "mlp_desc.h"
 
 namespace hgnn {
 
@@ -414,22 +415,14 @@ static int launch_b(const MlpArgsBf16& a, hipStream_t s) {
 
 using namespace hgnn;
 
+// 32-column k-blocks; inference only (no dumps), no pre-projected segments
+static const MlpDescRules kRulesBf16 = {/*seg_multiple*/ 32, /*padded_storage*/ false, /*layers*/ 2, 3,
+                                        /*ln_everywhere*/ true, /*save_pre*/ false, /*max_pre*/ 0, /*m_int32*/ false};
+
 extern "C" int hgnn_mlp_supported_bf16(const hgnn_mlp_desc* d) {
-    if (d == nullptr) return 0;
-    if (d->n_seg < 1 || d->n_seg > 3 || (d->n_layers != 2 && d->n_layers != 3)) return 0;
-    int k = 0;
-    for (int s = 0; s < d->n_seg; ++s) {
-        if (d->seg_width[s] <= 0 || d->seg_width[s] % 32 != 0) return 0;
-        k += d->seg_width[s];
-    }
-    if (k != d->width[0] || d->w0_cols != 0 || d->w_last_rows != 0) return 0;
-    const int n = d->n_layers;
-    for (int l = 0; l < n; ++l)
-        if (d->W[l] == nullptr || d->b[l] == nullptr || d->ln_w[l] == nullptr || d->ln_b[l] == nullptr) return 0;
-    if (d->save_pre[0] || d->save_pre[1] || d->save_pre[2] || d->n_pre != 0) return 0;
+    if (!mlp_desc_shape_ok(d, kRulesBf16)) return 0;
     const int h = d->width[1];
-    const int o = d->width[n];
-    if (n == 3 && d->width[2] != h) return 0;
+    const int o = d->width[d->n_layers];
     if (h != 2 * o) return 0;
     return (o == 32 || o == 64 || o == 128 || o == 256) ? 1 : 0;
 }
@@ -443,38 +436,12 @@ extern "C" int hgnn_mlp_forward_bf16(const hgnn_mlp_desc* d, void* out, hgnn_str
         return HGNN_ERR_UNSUPPORTED;
     }
     if (d->M == 0) return HGNN_OK;
-    HGNN_REQUIRE(d->M > 0, "hgnn_mlp_forward_bf16: bad M");
+    static const char fn[] = "hgnn_mlp_forward_bf16";
+    HGNN_REQUIRE(d->M > 0, "%s: bad M", fn);   // no upper bound here: only the fp32 entries have ever had one
     MlpArgsBf16 a;
-    for (int s = 0; s < 3; ++s) {
-        a.seg_table[s] = s < d->n_seg ? (const unsigned short*)d->seg_table[s] : nullptr;
-        a.seg_index[s] = s < d->n_seg ? d->seg_index[s] : nullptr;
-        a.seg_width[s] = s < d->n_seg ? d->seg_width[s] : 0;
-        if (s < d->n_seg) {
-            HGNN_REQUIRE(a.seg_table[s] != nullptr && (uintptr_t)a.seg_table[s] % 16 == 0,
-                         "hgnn_mlp_forward_bf16: segment table %d is NULL or not 16-byte aligned", s);
-        }
-    }
-    a.n_seg = d->n_seg;
-    a.K1 = d->width[0];
-    for (int l = 0; l < 3; ++l) {
-        const bool on = l < d->n_layers;
-        a.W[l] = on ? (const unsigned short*)d->W[l] : nullptr;
-        a.b[l] = on ? d->b[l] : nullptr;
-        a.lnw[l] = on ? d->ln_w[l] : nullptr;
-        a.lnb[l] = on ? d->ln_b[l] : nullptr;
-        a.act[l] = on ? d->act[l] : 0;
-        if (on) {
-            HGNN_REQUIRE((uintptr_t)a.W[l] % 16 == 0 && (uintptr_t)a.b[l] % 16 == 0 &&
-                             (uintptr_t)a.lnw[l] % 16 == 0 && (uintptr_t)a.lnb[l] % 16 == 0,
-                         "hgnn_mlp_forward_bf16: layer %d parameters must be 16-byte aligned", l);
-        }
-    }
-    a.eps = d->ln_eps;
-    a.skip = (const unsigned short*)d->skip;
-    a.out = (unsigned short*)out;
-    a.M = d->M;
-    HGNN_REQUIRE((uintptr_t)out % 8 == 0 && (uintptr_t)a.skip % 8 == 0,
-                 "hgnn_mlp_forward_bf16: out/skip must be 8-byte aligned");
+    HGNN_TRY(unpack_segments(a, d, fn));
+    for (int l = 0; l < 3; ++l) HGNN_TRY(unpack_layer(a, d, l, fn));
+    HGNN_TRY(unpack_out_skip(a, d, out, fn));
     const int o = d->width[d->n_layers];
     if (d->n_layers == 2) {
         switch (o) {

@@ -22,6 +22,7 @@
 //     rows by LDS-DMA, as in the bf16 kernel;
 //   * output / skip rows are fp32 (16 bytes per lane and tile).
 #include "mlp_split_common.h"
+#include "mlp_desc.h"
 #include "options.h"
 
 namespace hgnn {
@@ -716,24 +717,14 @@ static int launch(const Args& a, hipStream_t s) {
 
 using namespace hgnn;
 
+// 128-column input panels; the kernels index rows with 32 bits
+static const MlpDescRules kRulesF32Split3 = {/*seg_multiple*/ 128, /*padded_storage*/ false, /*layers*/ 2, 3,
+                                             /*ln_everywhere*/ true, /*save_pre*/ true, /*max_pre*/ 2, /*m_int32*/ true};
+
 extern "C" int hgnn_mlp_supported_f32_split3(const hgnn_mlp_desc* d) {
-    if (d == nullptr) return 0;
-    if (d->n_seg < 1 || d->n_seg > 3 || d->n_layers < 2 || d->n_layers > 3) return 0;
-    int k = 0;
-    for (int s = 0; s < d->n_seg; ++s) {
-        if (d->seg_width[s] <= 0 || d->seg_width[s] % 128 != 0) return 0;
-        k += d->seg_width[s];
-    }
-    if (k != d->width[0] || d->w0_cols != 0 || d->w_last_rows != 0) return 0;
+    if (!mlp_desc_shape_ok(d, kRulesF32Split3)) return 0;
     const int n = d->n_layers;
-    for (int l = 0; l < n; ++l)
-        if (d->W[l] == nullptr || d->b[l] == nullptr || d->ln_w[l] == nullptr || d->ln_b[l] == nullptr) return 0;
-    if (d->n_pre < 0 || d->n_pre > 2) return 0;
-    for (int s = 0; s < d->n_pre; ++s)
-        if (d->pre_table[s] == nullptr || d->pre_index[s] == nullptr) return 0;
-    if (d->M < 0 || d->M > 0x7fffffffLL) return 0;
     const int h = d->width[1], o = d->width[n];
-    if (n == 3 && d->width[2] != h) return 0;
     if (n == 2 && o == h) return (h == 256 || h == 512) ? 1 : 0;   // the two hidden layers of a score head
     if (h != 2 * o) return 0;
     return (o == 128 || o == 256) ? 1 : 0;
@@ -748,47 +739,19 @@ extern "C" int hgnn_mlp_forward_f32_split3(const hgnn_mlp_desc* d, float* out, h
         return HGNN_ERR_UNSUPPORTED;
     }
     if (d->M == 0) return HGNN_OK;
+    static const char fn[] = "hgnn_mlp_forward_f32_split3";
     f3::Args a;
-    for (int s = 0; s < 3; ++s) {
-        const bool on = s < d->n_seg;
-        a.seg_table[s] = on ? d->seg_table[s] : d->seg_table[0];
-        a.seg_index[s] = on ? d->seg_index[s] : nullptr;
-        a.seg_width[s] = on ? d->seg_width[s] : 0;
-        if (on) {
-            HGNN_REQUIRE(a.seg_table[s] != nullptr && (uintptr_t)a.seg_table[s] % 16 == 0,
-                         "hgnn_mlp_forward_f32_split3: segment table %d is NULL or not 16-byte aligned", s);
-        }
-    }
-    a.n_seg = d->n_seg;
-    a.K1 = d->width[0];
+    HGNN_TRY(unpack_segments(a, d, fn));
+    // unused slots repeat table 0 where the other entries pass NULL (as this entry always has: an address formed
+    // from an unused slot by the panel loads stays inside a real table)
+    for (int s = d->n_seg; s < 3; ++s) a.seg_table[s] = a.seg_table[0];
     for (int l = 0; l < 3; ++l) {
-        const bool on = l < d->n_layers;
-        a.W[l] = on ? (const unsigned short*)d->W[l] : nullptr;
-        a.b[l] = on ? d->b[l] : nullptr;
-        a.lnw[l] = on ? d->ln_w[l] : nullptr;
-        a.lnb[l] = on ? d->ln_b[l] : nullptr;
-        a.act[l] = on ? d->act[l] : 0;
-        a.save_pre[l] = on ? d->save_pre[l] : nullptr;
-        if (on) {
-            HGNN_REQUIRE((uintptr_t)a.W[l] % 16 == 0 && (uintptr_t)a.b[l] % 16 == 0 &&
-                             (uintptr_t)a.lnw[l] % 16 == 0 && (uintptr_t)a.lnb[l] % 16 == 0 &&
-                             (uintptr_t)a.save_pre[l] % 16 == 0,
-                         "hgnn_mlp_forward_f32_split3: layer %d parameters / save_pre must be 16-byte aligned", l);
-        }
+        HGNN_TRY(unpack_layer(a, d, l, fn));
+        HGNN_TRY(unpack_save_pre(a, d, l, fn));
     }
-    a.eps = d->ln_eps;
-    a.skip = d->skip;
-    a.out = out;
-    a.M = d->M;
     a.stagger = 0;
-    a.n_pre = d->n_pre;
-    for (int s = 0; s < 2; ++s) {
-        a.pre_table[s] = s < d->n_pre ? d->pre_table[s] : nullptr;
-        a.pre_index[s] = s < d->n_pre ? d->pre_index[s] : nullptr;
-        HGNN_REQUIRE((uintptr_t)a.pre_table[s] % 16 == 0, "hgnn_mlp_forward_f32_split3: pre_table[%d] must be 16-byte aligned", s);
-    }
-    HGNN_REQUIRE((uintptr_t)out % 16 == 0 && (uintptr_t)a.skip % 16 == 0,
-                 "hgnn_mlp_forward_f32_split3: out/skip must be 16-byte aligned");
+    HGNN_TRY(unpack_pre(a, d, fn));
+    HGNN_TRY(unpack_out_skip(a, d, out, fn));
     const int o = d->width[d->n_layers];
     if (d->n_layers == 2 && o == d->width[1])
         return o == 512 ? f3::launch<8, 4, 4, 2>(a, stream) : f3::launch<4, 4, 4, 2>(a, stream);

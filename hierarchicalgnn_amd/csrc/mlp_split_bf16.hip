@@ -20,6 +20,7 @@
 // GEMMs are transposed as in the other kernels (A = W fragment, B = activations, D[f][e]): lane
 // (e = lane&15, g = lane>>4) holds features 16T + 4g + r of edge 16j + e.
 #include "mlp_split_common.h"
+#include "mlp_desc.h"
 #include "options.h"
 
 namespace hgnn {
@@ -499,26 +500,16 @@ static int launch_single(const Args& a, hipStream_t s) {
 
 using namespace hgnn;
 
+// 128-column input panels; the kernel indexes rows with 32 bits
+static const MlpDescRules kRulesBf16Split = {/*seg_multiple*/ 128, /*padded_storage*/ false, /*layers*/ 1, 3,
+                                             /*ln_everywhere*/ true, /*save_pre*/ true, /*max_pre*/ 2, /*m_int32*/ true};
+
 extern "C" int hgnn_mlp_supported_bf16_split(const hgnn_mlp_desc* d) {
-    if (d == nullptr) return 0;
-    if (d->n_seg < 1 || d->n_seg > 3 || d->n_layers < 1 || d->n_layers > 3) return 0;
-    int k = 0;
-    for (int s = 0; s < d->n_seg; ++s) {
-        if (d->seg_width[s] <= 0 || d->seg_width[s] % 128 != 0) return 0;
-        k += d->seg_width[s];
-    }
-    if (k != d->width[0] || d->w0_cols != 0 || d->w_last_rows != 0) return 0;
+    if (!mlp_desc_shape_ok(d, kRulesBf16Split)) return 0;
     const int n = d->n_layers;
-    for (int l = 0; l < n; ++l)
-        if (d->W[l] == nullptr || d->b[l] == nullptr || d->ln_w[l] == nullptr || d->ln_b[l] == nullptr) return 0;
-    if (d->n_pre < 0 || d->n_pre > 2) return 0;
-    for (int s = 0; s < d->n_pre; ++s)
-        if (d->pre_table[s] == nullptr || d->pre_index[s] == nullptr) return 0;
-    if (d->M < 0 || d->M > 0x7fffffffLL) return 0;
     const int h = d->width[1];
     const int o = d->width[n];
     if (n == 1) return (o == 256 || o == 512 || o == 1024) && d->n_pre == 0 ? 1 : 0;   // single layers (chains)
-    if (n == 3 && d->width[2] != h) return 0;
     if (h != 2 * o) return 0;
     return (o == 128 || o == 256 || o == 512) ? 1 : 0;
 }
@@ -532,48 +523,14 @@ extern "C" int hgnn_mlp_forward_bf16_split(const hgnn_mlp_desc* d, void* out, hg
         return HGNN_ERR_UNSUPPORTED;
     }
     if (d->M == 0) return HGNN_OK;
+    static const char fn[] = "hgnn_mlp_forward_bf16_split";
     fs::Args a;
-    for (int s = 0; s < 3; ++s) {
-        a.seg_table[s] = s < d->n_seg ? (const unsigned short*)d->seg_table[s] : nullptr;
-        a.seg_index[s] = s < d->n_seg ? d->seg_index[s] : nullptr;
-        a.seg_width[s] = s < d->n_seg ? d->seg_width[s] : 0;
-        if (s < d->n_seg) {
-            HGNN_REQUIRE(a.seg_table[s] != nullptr && (uintptr_t)a.seg_table[s] % 16 == 0,
-                         "hgnn_mlp_forward_bf16_split: segment table %d is NULL or not 16-byte aligned", s);
-        }
-    }
-    a.n_seg = d->n_seg;
-    a.K1 = d->width[0];
-    for (int l = 0; l < 3; ++l) {
-        const bool on = l < d->n_layers;
-        a.W[l] = on ? (const unsigned short*)d->W[l] : nullptr;
-        a.b[l] = on ? d->b[l] : nullptr;
-        a.lnw[l] = on ? d->ln_w[l] : nullptr;
-        a.lnb[l] = on ? d->ln_b[l] : nullptr;
-        a.act[l] = on ? d->act[l] : 0;
-        if (on) {
-            HGNN_REQUIRE((uintptr_t)a.W[l] % 16 == 0 && (uintptr_t)a.b[l] % 16 == 0 &&
-                             (uintptr_t)a.lnw[l] % 16 == 0 && (uintptr_t)a.lnb[l] % 16 == 0,
-                         "hgnn_mlp_forward_bf16_split: layer %d parameters must be 16-byte aligned", l);
-        }
-    }
-    a.eps = d->ln_eps;
-    a.skip = (const unsigned short*)d->skip;
-    a.out = (unsigned short*)out;
-    a.M = d->M;
-    a.n_pre = d->n_pre;
-    for (int s = 0; s < 2; ++s) {
-        a.pre_table[s] = s < d->n_pre ? (const unsigned short*)d->pre_table[s] : nullptr;
-        a.pre_index[s] = s < d->n_pre ? d->pre_index[s] : nullptr;
-        HGNN_REQUIRE((uintptr_t)a.pre_table[s] % 16 == 0, "hgnn_mlp_forward_bf16_split: pre_table[%d] must be 16-byte aligned", s);
-    }
+    HGNN_TRY(unpack_segments(a, d, fn));
+    for (int l = 0; l < 3; ++l) HGNN_TRY(unpack_layer(a, d, l, fn));
+    HGNN_TRY(unpack_pre(a, d, fn));
     a.ablate = g_opt_mlp_ablate;
-    for (int l = 0; l < 3; ++l) {
-        a.save_pre[l] = l < d->n_layers ? (unsigned short*)d->save_pre[l] : nullptr;   // bf16 rows here
-        HGNN_REQUIRE((uintptr_t)a.save_pre[l] % 8 == 0, "hgnn_mlp_forward_bf16_split: save_pre[%d] must be 8-byte aligned", l);
-    }
-    HGNN_REQUIRE((uintptr_t)out % 8 == 0 && (uintptr_t)a.skip % 8 == 0,
-                 "hgnn_mlp_forward_bf16_split: out/skip must be 8-byte aligned");
+    for (int l = 0; l < 3; ++l) HGNN_TRY(unpack_save_pre(a, d, l, fn));   // bf16 rows here
+    HGNN_TRY(unpack_out_skip(a, d, out, fn));
     const int o = d->width[d->n_layers];
     if (d->n_layers == 1) {
         if (o == 256) return fs::launch_single<4, 2, 4>(a, stream);

@@ -190,6 +190,114 @@ def _padded_param(param, rows: int, cols: Optional[int] = None, kept_cols=None, 
     return _cached(param, ("f32_padded", rows, cols, kept_cols, k_cols), make)
 
 
+# One function per kernel: the weight layout of layer ``l`` of ``n`` (modules ``lin``, ``ln``; ``raw``: their W, b, ln_w,
+# ln_b, the Parameters themselves).  ``cols``: the column blocks that stay in the kernel's K loop (first layer with
+# pre-projected segments, else None), ``K`` wide (= width[0]); ``small_k``: first layer, K <= 16 stored as one 16-column
+# chunk; ``hidden``: the first layer's output width; ``P_grid`` (f32_padded): the grid width the network runs on.
+# Returns (w0_cols, w_last_rows, make) -- the descriptor fields the layout implies (0 = none) and ``make()`` -> the
+# prepared (W, b, ln_w, ln_b), which a dry descriptor skips -- or None when the kernel has no such layer.  Plain
+# arguments and no work outside ``make``: this runs for every layer of every call.
+def _layout_f32(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
+    """fp32 weights as they are; zero padded where the kernel wants more than the layer has"""
+    o, last, rows = int(lin.out_features), l == n - 1, 0
+    if last and ln is None:
+        # head (width-1 classifiers, emb_dim-wide embedding head): the plain last layer is stored zero-padded as 32 rows
+        if o > 32:
+            return None
+        rows = 32
+    elif last and n == 3 and o not in (32, 64, 128, 256) and hidden % 2 == 0:
+        # narrower than its tile row (supernode encoder, L - emb_dim outputs): Linear / LayerNorm parameters
+        # zero-padded to P = hidden / 2 rows; the kernel normalises over the real width
+        rows = hidden // 2
+        if not (rows - 16 < o < rows) or o % 4:
+            return None
+    elif n == 1 and ln is not None and 496 < o < 512 and o % 4 == 0:
+        # the narrow last layer of a chain (supernode encoder at latent 512, 504 outputs): one single-layer launch on
+        # parameters zero-padded to 512 rows, statistics and stores over the real width
+        rows = 512
+
+    def make():
+        if not (cols or small_k or rows):
+            return raw
+        W = raw[0].detach()
+        if cols:
+            W = torch.cat([W[:, c0:c1] for c0, c1 in cols], dim=1).contiguous()
+        if small_k:
+            # small-K mode (encoders, K = 3 / 6): one zero-padded 16-column chunk
+            W = torch.nn.functional.pad(W, (0, 16 - K)).contiguous()
+        ps = (W,) + raw[1:]
+        return ps if not rows else [p if p is None else _pad_rows(p.detach(), rows) for p in ps]
+    return 16 if small_k else 0, rows, make
+
+
+def _layout_f32_padded(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
+    """widths between the grid's: every parameter zero padded to the instantiation of P_grid (layout:
+    hgnn_mlp_supported_f32_padded in include/hgnn_hip.h); cached copies, the kernel's statistics, dumps and stores use
+    the real widths in d.width"""
+    last = l == n - 1
+    rows = 32 if ln is None else (P_grid if last else 2 * P_grid)
+
+    def make():
+        W = _padded_param(lin.weight, rows, 2 * P_grid if l > 0 else None, cols, 16 if small_k else None)
+        lnp = (None, None) if ln is None else (_padded_param(ln.weight, rows), _padded_param(ln.bias, rows))
+        return (W, _padded_param(lin.bias, rows)) + lnp
+    return 16 if small_k else 0, rows if last else 0, make
+
+
+def _layout_f32_split3(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
+    """the bf16 split stream of the fp32 weight"""
+    if ln is None or small_k:
+        return None
+    return 0, 0, lambda: (_split3_weight(lin.weight, cols, l == 0),) + raw[1:]
+
+
+def _layout_bf16(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
+    """bf16 [out][in], layers >= 1 in k-slot column order"""
+    if l > 0 and lin.in_features % 32:
+        return None
+
+    def make():
+        W = raw[0].detach()
+        return ((W[:, _kslot_perm(lin.in_features, W.device)] if l > 0 else W).to(torch.bfloat16).contiguous(),) + raw[1:]
+    return 0, 0, make
+
+
+def _layout_bf16_split(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
+    """bf16 in A-fragment order"""
+    if (K if cols else lin.in_features) % 32 or lin.out_features % 64:
+        return None
+    return 0, 0, lambda: (_prepared_weight(lin.weight, cols),) + raw[1:]
+
+
+_LAYOUTS = {"f32": _layout_f32, "f32_padded": _layout_f32_padded, "f32_split3": _layout_f32_split3,
+            "bf16": _layout_bf16, "bf16_split": _layout_bf16_split}
+
+
+def _preprojections(tables, cols, proj, lin0, bf16: bool, split_proj: bool, width: int):
+    """{i: tables[i] W_i^T  [rows, H]} for i in ``proj`` (W_i: columns ``cols[i]`` of the first Linear), zero padded to
+    ``width`` columns (f32_padded: the padded W[0] rows).  ``split_proj``: by ``_split3_project`` where it has the shape"""
+    P = {}
+    if split_proj and proj:
+        # both segments of one table (nodes[graph[0]], nodes[graph[1]]) in one launch
+        t0 = tables[proj[0]]
+        same = len(proj) == 2 and tables[proj[1]].data_ptr() == t0.data_ptr() and tables[proj[1]].shape == t0.shape
+        for grp in ([proj] if same else [[i] for i in proj]):
+            res = _split3_project(tables[grp[0]].detach(), lin0.weight, [cols[i] for i in grp])
+            if res is not None:
+                P.update(zip(grp, res))
+    for i in proj:
+        if i in P:
+            continue
+        W_s = lin0.weight.detach()[:, cols[i][0]:cols[i][1]]
+        with torch.autocast("cuda", enabled=False):
+            # the kernel reads P in its row dtype; bf16: bf16 operands, fp32 accumulation, one rounding -- the
+            # arithmetic the kernel's own MFMAs would do
+            P[i] = torch.matmul(tables[i].detach(), (W_s.to(torch.bfloat16) if bf16 else W_s).t())
+        if width and int(P[i].shape[1]) < width:
+            P[i] = torch.nn.functional.pad(P[i], (0, width - int(P[i].shape[1])))
+    return P
+
+
 def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = False, dry: bool = False, layers=None):
     """(descriptor, keep-alive list, M, n_out) for ``hgnn_mlp_forward_<entry>`` (``entry`` in f32, f32_padded,
     f32_split3, bf16, bf16_split), or None.  ``layers``: ``_parse(net)`` when the caller has it (then ``net`` is not read).
@@ -198,173 +306,80 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
     ``hgnn_mlp_desc.n_pre`` vs the ones kept in the kernel's K loop), the layers (chained widths, one LayerNorm eps)
     and the skip rows.  What depends on the kernel: the row dtype, which segments are pre-projected (fp32: by
     ``_projected_segments``; bf16: only for the split kernel, by ``preproject_bf16``, P rounded once to bf16) and the
-    weight layout of each layer (below).  ``dry``: only decide supportability (no projection GEMM or weight
-    preparation runs; the descriptor must not be launched).  ``split_proj`` (f32_split3): the N-row projection GEMMs
-    use the consuming kernel's arithmetic (hgnn_project_f32_split3, three products) instead of the library's fp32 GEMM."""
+    weight layout of each layer (``_LAYOUTS[entry]``).  ``dry``: only decide supportability (no projection GEMM or
+    weight preparation runs: the tables and the module's own parameters stand in; the descriptor must not be launched).
+    ``split_proj`` (f32_split3): the N-row projection GEMMs use the consuming kernel's arithmetic
+    (hgnn_project_f32_split3, three products) instead of the library's fp32 GEMM."""
     bf16 = entry.startswith("bf16")
-    split = entry == "bf16_split"
     dt = torch.bfloat16 if bf16 else torch.float32
     layers = _parse(net) if layers is None else layers
     if layers is None or not (1 <= len(layers) <= 3 and 1 <= len(segments) <= 3):
         return None
-    if any(ln is None for _, ln, _ in (layers if bf16 else layers[:-1])):
+    if any(ln is None for _, ln, _ in (layers if bf16 else layers[:-1])) \
+            or any(t.dim() != 2 or not t.is_cuda or t.dtype != dt for t, _ in segments):
         return None
-    d = _lib.HgnnMlpDesc()
-    keep = []
-    M = None
-    for table, index in segments:
-        if table.dim() != 2 or not table.is_cuda or table.dtype != dt:
-            return None
-        rows = int(index.numel()) if index is not None else int(table.shape[0])
-        if M is None:
-            M = rows
-        elif M != rows:
-            return None
+    M, *more = {int(i.numel()) if i is not None else int(t.shape[0]) for t, i in segments}
+    ws = [int(t.shape[1]) for t, _ in segments]
     lin0 = layers[0][0]
-    if lin0.in_features != sum(int(t.shape[1]) for t, _ in segments) or not lin0.weight.is_cuda:
+    if more or lin0.in_features != sum(ws) or not lin0.weight.is_cuda:
         return None
-    padded = entry == "f32_padded"
-    P_grid = _pad_grid(int(lin0.out_features)) if padded else 0
-    if padded and (P_grid == 0 or len(layers) < 2):
+    hidden = int(lin0.out_features)
+    P_grid = _pad_grid(hidden) if entry == "f32_padded" else 0
+    if entry == "f32_padded" and (P_grid == 0 or len(layers) < 2):
         return None
     if bf16:
         pre = _opt("preproject_bf16")
-        pre = split and (len(layers) > 1 and lin0.out_features >= 512 if pre is None else pre)
+        pre = entry == "bf16_split" and (len(layers) > 1 and hidden >= 512 if pre is None else pre)
     else:
         pre = layers[0][1] is not None
     proj = _projected_segments(segments, M) if pre else []
-    split_P = {}
-    if split_proj and proj and not dry:
-        # the pre-projections in the consuming kernel's own arithmetic; both segments of one table (nodes[graph[0]],
-        # nodes[graph[1]]) in one launch
-        cols, c0 = {}, 0
-        for i, (t, _) in enumerate(segments):
-            cols[i] = (c0, c0 + int(t.shape[1]))
-            c0 += int(t.shape[1])
-        t0 = segments[proj[0]][0]
-        same = len(proj) == 2 and segments[proj[1]][0].data_ptr() == t0.data_ptr() \
-            and segments[proj[1]][0].shape == t0.shape and t0.is_contiguous() and segments[proj[1]][0].is_contiguous()
-        groups = [proj] if same else [[i] for i in proj]
-        for grp in groups:
-            res = _split3_project(segments[grp[0]][0].detach(), lin0.weight, [cols[i] for i in grp])
-            if res is not None:
-                split_P.update(dict(zip(grp, res)))
-    col = n_kept = n_pre = 0
-    kept_cols = []
-    for i, (table, index) in enumerate(segments):
-        t = table if table.is_contiguous() else table.contiguous()
-        keep.append(t)
-        w = int(t.shape[1])
-        i32 = None
-        if index is not None:
-            i32 = get_index32(index, int(t.shape[0]))
-            keep.append(i32)
+    tables = [t if t.is_contiguous() else t.contiguous() for t, _ in segments]
+    cols = [(sum(ws[:i]), sum(ws[:i + 1])) for i in range(len(ws))]
+    pre_rows = _preprojections(tables, cols, proj, lin0, bf16, split_proj, 2 * P_grid) if proj and not dry else {}
+    d = _lib.HgnnMlpDesc()
+    keep = []
+    n_kept = n_pre = 0
+    for i, (t, (_, index)) in enumerate(zip(tables, segments)):
+        i32 = None if index is None else get_index32(index, int(t.shape[0]))
+        i_ptr = i32.data_ptr() if i32 is not None and i32.numel() else None
+        keep += [t] if i32 is None else [t, i32]
         if i in proj:
-            if dry:
-                P = t
-            else:
-                P = split_P.get(i)
-                if P is None:
-                    W_s = lin0.weight.detach()[:, col:col + w]
-                    with torch.autocast("cuda", enabled=False):
-                        # the kernel reads P in its row dtype; bf16: bf16 operands, fp32 accumulation, one rounding --
-                        # the arithmetic the kernel's own MFMAs would do
-                        P = torch.matmul(t.detach(), (W_s.to(torch.bfloat16) if bf16 else W_s).t())   # [rows, H]
-                    if padded and int(P.shape[1]) < 2 * P_grid:
-                        P = torch.nn.functional.pad(P, (0, 2 * P_grid - int(P.shape[1])))   # the padded W[0] rows: zeros
-                keep.append(P)
-            d.pre_table[n_pre] = P.data_ptr()
-            d.pre_index[n_pre] = i32.data_ptr() if i32.numel() else None
+            P = pre_rows.get(i, t)
+            keep.append(P)
+            d.pre_table[n_pre], d.pre_index[n_pre] = P.data_ptr(), i_ptr
             n_pre += 1
         else:
-            d.seg_table[n_kept] = t.data_ptr()
-            d.seg_width[n_kept] = w
-            d.seg_index[n_kept] = (i32.data_ptr() if i32.numel() else None) if i32 is not None else None
-            kept_cols.append((col, col + w))
+            d.seg_table[n_kept], d.seg_index[n_kept], d.seg_width[n_kept] = t.data_ptr(), i_ptr, ws[i]
             n_kept += 1
-        col += w
     d.n_seg, d.n_pre = n_kept, n_pre
-    n = len(layers)
-    d.n_layers = n
-    K = sum(c1 - c0 for c0, c1 in kept_cols)
-    d.width[0] = K
+    # the kernel's K loop only sees the kept segments
+    kept_cols = tuple(c for i, c in enumerate(cols) if i not in proj) if proj else None
+    n = d.n_layers = len(layers)
+    o_l = K = d.width[0] = sum(ws) - sum(ws[i] for i in proj)
+    small_k = not bf16 and any(w % 16 for w in ws)
+    if small_k and K > 16:
+        return None
     eps = None
     for l, (lin, ln, act) in enumerate(layers):
-        if l > 0 and lin.in_features != d.width[l]:
+        if l > 0 and lin.in_features != o_l:
             return None
-        cols = tuple(kept_cols) if (l == 0 and n_pre) else None    # the kernel's K loop only sees the kept segments
-        W, b = lin.weight.detach(), lin.bias.detach()
-        lnw, lnb = (ln.weight.detach(), ln.bias.detach()) if ln is not None else (None, None)
-        o_l = int(lin.out_features)
-        if bf16:
-            # bf16 copies of the weights: A-fragment order (split kernel) or k-slot column order (W_{l>=1}); bias and
-            # LayerNorm parameters in fp32
-            if not W.is_cuda:
+        # the Parameters themselves: only a layout that re-lays one out detaches it
+        raw = (lin.weight, lin.bias) + ((None, None) if ln is None else (ln.weight, ln.bias))
+        if not raw[0].is_cuda:
+            return None
+        for p in () if bf16 else raw:             # fp32 kernels: the parameters as they are
+            if p is not None and (not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous()):
                 return None
-            if split:
-                if (K if cols else lin.in_features) % 32 or o_l % 64:
-                    return None
-                if not dry:
-                    W = _prepared_weight(lin.weight, cols)
-            else:
-                if l > 0 and lin.in_features % 32:
-                    return None
-                if not dry:
-                    W = (W[:, _kslot_perm(lin.in_features, W.device)] if l > 0 else W).to(torch.bfloat16).contiguous()
-            b, lnw, lnb = (p.float().contiguous() for p in (b, lnw, lnb))
-        else:
-            # fp32 weights as they are (f32_split3: their bf16 split stream), padded where the kernel wants more
-            if any(not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous()
-                   for p in (W, b) + ((lnw, lnb) if ln is not None else ())):
-                return None
-            small_k = l == 0 and any(int(t.shape[1]) % 16 for t, _ in segments)
-            if small_k and K > 16:
-                return None
-            if padded:
-                # widths between the grid's: every parameter zero padded to the instantiation of P_grid (layout:
-                # hgnn_mlp_supported_f32_padded in include/hgnn_hip.h); cached copies, the kernel's statistics, dumps
-                # and stores use the real widths in d.width
-                rows = 32 if ln is None else (P_grid if l == n - 1 else 2 * P_grid)
-                if small_k:
-                    d.w0_cols = 16
-                if l == n - 1:
-                    d.w_last_rows = rows
-                if not dry:
-                    W = _padded_param(lin.weight, rows, 2 * P_grid if l > 0 else None, cols, 16 if small_k else None)
-                    b = _padded_param(lin.bias, rows)
-                    if ln is not None:
-                        lnw, lnb = _padded_param(ln.weight, rows), _padded_param(ln.bias, rows)
-            elif entry == "f32_split3" and not dry:
-                W = _split3_weight(lin.weight, cols, l == 0)
-            elif cols and not dry:
-                W = torch.cat([W[:, c0:c1] for c0, c1 in cols], dim=1).contiguous()
-            if small_k and not padded:
-                # small-K mode (encoders, K = 3 / 6): one zero-padded 16-column chunk
-                W = torch.nn.functional.pad(W, (0, 16 - K)).contiguous()
-                d.w0_cols = 16
-            if padded:
-                pass                                      # stored rows and w_last_rows are set above
-            elif l == n - 1 and ln is None:
-                if o_l > 32:
-                    return None
-                # head (width-1 classifiers, emb_dim-wide embedding head): the plain last layer is stored
-                # zero-padded as 32 rows
-                W, b = _pad_rows(W, 32), _pad_rows(b, 32)
-                d.w_last_rows = 32
-            elif l == n - 1 and n == 3 and o_l not in (32, 64, 128, 256) and layers[0][0].out_features % 2 == 0:
-                # narrower than its tile row (supernode encoder, L - emb_dim outputs): Linear / LayerNorm
-                # parameters zero-padded to P = hidden / 2 rows; the kernel normalises over the real width
-                P = layers[0][0].out_features // 2
-                if not (P - 16 < o_l < P) or o_l % 4:
-                    return None
-                W, b, lnw, lnb = (_pad_rows(p, P) for p in (W, b, lnw, lnb))
-                d.w_last_rows = P
-            elif n == 1 and ln is not None and 496 < o_l < 512 and o_l % 4 == 0:
-                # the narrow last layer of a chain (supernode encoder at latent 512, 504 outputs): one single-layer
-                # launch on parameters zero-padded to 512 rows, statistics and stores over the real width
-                if not dry:
-                    W, b, lnw, lnb = (_pad_rows(p, 512) for p in (W, b, lnw, lnb))
-                d.w_last_rows = 512
+        if bf16:                                  # the bf16 kernels read bias and LayerNorm parameters in fp32
+            raw = raw[:1] + tuple(p.detach().float().contiguous() for p in raw[1:])
+        lay = _LAYOUTS[entry](l, n, lin, ln, raw, kept_cols if l == 0 else None, K, small_k and l == 0, hidden, P_grid)
+        if lay is None:
+            return None
+        if lay[0]:
+            d.w0_cols = lay[0]
+        if lay[1]:
+            d.w_last_rows = lay[1]
+        W, b, lnw, lnb = raw if dry else lay[2]()
         keep += [W, b, lnw, lnb]
         d.W[l], d.b[l] = W.data_ptr(), b.data_ptr()
         if ln is not None:
@@ -373,9 +388,7 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
                 eps = ln.eps
             elif eps != ln.eps:
                 return None
-        else:
-            d.ln_w[l] = d.ln_b[l] = None
-        d.width[l + 1] = o_l
+        o_l = d.width[l + 1] = int(lin.out_features)
         d.act[l] = act
     d.ln_eps = float(eps)
     n_out = int(d.width[n])
@@ -385,8 +398,6 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
         sk = skip if skip.is_contiguous() else skip.contiguous()
         keep.append(sk)
         d.skip = sk.data_ptr()
-    else:
-        d.skip = None
     d.M = M
     return d, keep, M, n_out
 
@@ -927,6 +938,40 @@ def _zero_grads(ctx, tables, params, grad_out, n_seg):
     return (None, None, None, *gt, *gs, *[torch.zeros_like(p) for p in params])
 
 
+def _train_forward(ctx, route, indices, has_skip, tensors):
+    """the forward of both differentiable variants (``tensors`` = tables, the skip rows if any, then W, b, ln_w, ln_b
+    of every layer): the kernel of ``route.entry`` dumping each layer's pre-LayerNorm rows z_l (``save_pre``) in the
+    row dtype; fills ``ctx`` for the backward.  Returns (out, tables, skip, [z_l])"""
+    n_seg = len(indices)
+    tables = list(tensors[:n_seg])
+    skip = tensors[n_seg] if has_skip else None
+    params = tensors[n_seg + (1 if has_skip else 0):]
+    bf16 = route.entry.startswith("bf16")
+    desc = _descriptor(route.net, list(zip(tables, indices)), skip, route.entry, layers=route.layers)
+    if desc is None:
+        raise RuntimeError(f"fused_concat_mlp_train{' (bf16)' if bf16 else ''}: unsupported arguments "
+                           "(call supported_train() first)")
+    d, keep, M, n_out = desc
+    # a score head: the LayerNorm'ed hidden layers are differentiated here, the plain last Linear is applied by the
+    # caller on the returned hidden rows (``_run``)
+    n = int(d.n_layers) - (1 if route.head else 0)
+    dt, dev = torch.bfloat16 if bf16 else torch.float32, tables[0].device
+    zs = [torch.empty((M, int(d.width[l + 1])), dtype=dt, device=dev) for l in range(n)]
+    for l in range(n):
+        d.save_pre[l] = zs[l].data_ptr() if M else None
+    out = torch.empty((M, n_out), dtype=dt, device=dev)
+    if M:
+        with torch.cuda.device(dev):
+            # f32_split3 (opt-in): the forward and its dumps on the split-bf16 kernel; the backward is unchanged
+            _forward(route.entry, d, out, dev)
+    del keep
+    stats["fused_train_calls"] += 1
+    ctx.indices, ctx.has_skip, ctx.n, ctx.net, ctx.layers = indices, has_skip, n, route.net, route.layers
+    ctx.acts, ctx.eps = [int(d.act[l]) for l in range(n)], float(d.ln_eps)
+    ctx.save_for_backward(*tables, *params, *zs)
+    return out, tables, skip, zs
+
+
 class _FusedMLPTrain(torch.autograd.Function):
     """Differentiable fused MLP.  Forward = the same MFMA kernel, additionally dumping each layer's
     pre-LayerNorm output z_l (``save_pre``).  Backward is written out by hand: LayerNorm / activation
@@ -938,39 +983,11 @@ class _FusedMLPTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, route, indices, has_skip, *tensors):
-        n_seg = len(indices)
-        tables = list(tensors[:n_seg])
-        skip = tensors[n_seg] if has_skip else None
-        params = tensors[n_seg + (1 if has_skip else 0):]
-        segments = [(t, i) for t, i in zip(tables, indices)]
-        desc = _descriptor(route.net, segments, skip, route.entry, layers=route.layers)
-        if desc is None:
-            raise RuntimeError("fused_concat_mlp_train: unsupported arguments (call supported_train() first)")
-        d, keep, M, n_out = desc
-        n = int(d.n_layers)
-        if route.head:
-            n -= 1             # a score head: the LayerNorm'ed hidden layers are differentiated here, the plain last
-                               # Linear is applied by the caller on the returned hidden rows (``_run``)
-        dev = tables[0].device
-        zs = [torch.empty((M, int(d.width[l + 1])), dtype=torch.float32, device=dev) for l in range(n)]
-        for l in range(n):
-            d.save_pre[l] = zs[l].data_ptr() if M else None
-        out = torch.empty((M, n_out), dtype=torch.float32, device=dev)
-        if M:
-            with torch.cuda.device(dev):
-                # f32_split3 (opt-in): the forward and its dumps on the split-bf16 kernel; the backward is unchanged
-                _forward(route.entry, d, out, dev)
-        del keep
-        stats["fused_train_calls"] += 1
-        ctx.indices, ctx.has_skip, ctx.n = indices, has_skip, n
-        ctx.net, ctx.layers = route.net, route.layers
-        ctx.acts = [int(d.act[l]) for l in range(n)]
-        ctx.eps = float(d.ln_eps)
-        ctx.save_for_backward(*tables, *params, *zs)
+        out, _, _, zs = _train_forward(ctx, route, indices, has_skip, tensors)
         if route.head:
             # the hidden rows feeding the plain last Linear: one LayerNorm / activation row pass over the last dump
-            ln = route.layers[n - 1][1]
-            return _ln_act_forward(zs[n - 1], ln.weight, ln.bias, ctx.acts[n - 1], ctx.eps)
+            ln = route.layers[ctx.n - 1][1]
+            return _ln_act_forward(zs[-1], ln.weight, ln.bias, ctx.acts[-1], ctx.eps)
         return out
 
     @staticmethod
@@ -1165,38 +1182,15 @@ class _FusedMLPTrainBf16(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, route, indices, has_skip, *tensors):
-        n_seg = len(indices)
-        tables = list(tensors[:n_seg])
-        skip = tensors[n_seg] if has_skip else None
-        params = tensors[n_seg + (1 if has_skip else 0):]
-        segments = [(t, i) for t, i in zip(tables, indices)]
-        desc = _descriptor(route.net, segments, skip, route.entry, layers=route.layers)
-        if desc is None:
-            raise RuntimeError("fused_concat_mlp_train (bf16): unsupported arguments (call supported_train() first)")
-        d, keep, M, n_out = desc
-        n = int(d.n_layers)
-        dev = tables[0].device
-        zs = [torch.empty((M, int(d.width[l + 1])), dtype=torch.bfloat16, device=dev) for l in range(n)]
-        for l in range(n):
-            d.save_pre[l] = zs[l].data_ptr() if M else None
-        out = torch.empty((M, n_out), dtype=torch.bfloat16, device=dev)
-        if M:
-            with torch.cuda.device(dev):
-                _forward(route.entry, d, out, dev)
-        del keep
-        stats["fused_train_calls"] += 1
-        ctx.indices, ctx.has_skip, ctx.n = indices, has_skip, n
-        ctx.acts = [int(d.act[l]) for l in range(n)]
-        ctx.eps = float(d.ln_eps)
+        out, tables, skip, _ = _train_forward(ctx, route, indices, has_skip, tensors)
         # skip is the same tensor as a direct (un-gathered) segment: its gradient is folded into that segment's
         ctx.skip_seg = -1
         if has_skip:
-            for s_i in range(n_seg):
+            for s_i in range(len(indices)):
                 t = tables[s_i]
-                if indices[s_i] is None and ctx.needs_input_grad[3 + s_i] and ctx.needs_input_grad[3 + n_seg] \
+                if indices[s_i] is None and ctx.needs_input_grad[3 + s_i] and ctx.needs_input_grad[3 + len(indices)] \
                         and t.data_ptr() == skip.data_ptr() and t.shape == skip.shape and t.stride() == skip.stride():
                     ctx.skip_seg = s_i
-        ctx.save_for_backward(*tables, *params, *zs)
         return out
 
     @staticmethod

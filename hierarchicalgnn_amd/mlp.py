@@ -25,6 +25,24 @@ from .ops import gather_rows
 Segment = Tuple[torch.Tensor, Optional[torch.Tensor]]  # (table, index or None)
 
 
+def _hybrid(net, segments, skip, train: bool):
+    """the hybrid chain of the encoders in bf16 latent mode: the first Linear -> LayerNorm -> act on the fp32 rows,
+    the cast, the rest on bf16 rows; None unless a fused route exists for both"""
+    from . import fused
+    if skip is not None or len(net) <= 3 or train != torch.is_grad_enabled() or not fused._opt("enabled") \
+            or not all(t.dtype == torch.float32 and t.is_cuda for t, _ in segments):
+        return None
+    first, rest = nn.Sequential(*list(net)[:3]), nn.Sequential(*list(net)[3:])
+    r_first = fused._route(first, segments, None, train=train)
+    probe = [(torch.empty((0, net[0].out_features), dtype=torch.bfloat16, device=segments[0][0].device), None)]
+    r_rest = None if r_first is None else fused._route(rest, probe, None, train=train)
+    if r_rest is None:
+        return None
+    if train:
+        fused.stats["hybrid_train_calls"] += 1
+    return fused._run(r_rest, [(fused._run(r_first, segments, None).to(torch.bfloat16), None)], None)
+
+
 def concat_mlp(net: nn.Sequential, segments: Sequence[Segment], skip: Optional[torch.Tensor] = None,
                bf16_tail: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``bf16_tail`` (bf16 latent mode, encoders): when an fp32-input MLP has no fused kernel, keep its
@@ -40,35 +58,22 @@ def concat_mlp(net: nn.Sequential, segments: Sequence[Segment], skip: Optional[t
         if r is not None:
             return fused._run(r, segments, skip, out=out)
         return out.copy_(concat_mlp(net, segments, skip, bf16_tail))
-    if bf16_tail and skip is None and len(net) > 3 and not torch.is_grad_enabled() and fused._opt("enabled") \
-            and all(t.dtype == torch.float32 for t, _ in segments):
-        # bf16 latent mode, encoders: hybrid chain -- the first Linear (hit coordinates: must not be rounded to 8
-        # bits) as ONE fp32 fused layer, the wide tail on the bf16 feature-split kernel (edge encoder at latent 256,
-        # 2M rows: 3.0 instead of 5.6 ms for the all-fp32 fused kernel)
-        first, rest = nn.Sequential(*list(net)[:3]), nn.Sequential(*list(net)[3:])
-        r_first = fused._route(first, segments, None, train=False)
-        probe = [(torch.empty((0, net[0].out_features), dtype=torch.bfloat16, device=segments[0][0].device), None)]
-        r_rest = None if r_first is None else fused._route(rest, probe, None, train=False)
-        if r_rest is not None:
-            y = fused._run(r_first, segments, None)
-            return fused._run(r_rest, [(y.to(torch.bfloat16), None)], None)
+    # bf16 latent mode, encoders: hybrid chain -- the first Linear (hit coordinates: must not be rounded to 8 bits) as
+    # ONE fp32 fused layer, the wide tail on the bf16 feature-split kernel (edge encoder at latent 256, 2M rows: 3.0
+    # instead of 5.6 ms for the all-fp32 fused kernel)
+    y = _hybrid(net, segments, skip, train=False) if bf16_tail else None
+    if y is not None:
+        return y
     r = fused._route(net, segments, skip, train=False, allow_chain=not bf16_tail) \
         or fused._route(net, segments, skip, train=True)
     if r is not None:
         return fused._run(r, segments, skip)
-    if bf16_tail and skip is None and len(net) > 3 and torch.is_grad_enabled() and fused._opt("enabled") \
-            and all(t.dtype == torch.float32 and t.is_cuda for t, _ in segments):
-        # the same hybrid chain under autograd (encoders at latent 512, whose 1024-wide hidden layers have no fp32
-        # training kernel): the first Linear as ONE differentiable fp32 layer (small-K, dump at its real width), the
-        # cast, the wide tail on the differentiable bf16 feature-split kernel -- only when both routes exist
-        first, rest = nn.Sequential(*list(net)[:3]), nn.Sequential(*list(net)[3:])
-        r_first = fused._route(first, segments, None, train=True)
-        probe = [(torch.empty((0, net[0].out_features), dtype=torch.bfloat16, device=segments[0][0].device), None)]
-        r_rest = None if r_first is None else fused._route(rest, probe, None, train=True)
-        if r_rest is not None:
-            fused.stats["hybrid_train_calls"] += 1
-            y = fused._run(r_first, segments, None)
-            return fused._run(r_rest, [(y.to(torch.bfloat16), None)], None)
+    # the same hybrid chain under autograd (encoders at latent 512, whose 1024-wide hidden layers have no fp32 training
+    # kernel): the first Linear as ONE differentiable fp32 layer (small-K, dump at its real width), the cast, the wide
+    # tail on the differentiable bf16 feature-split kernel -- only when both routes exist
+    y = _hybrid(net, segments, skip, train=True) if bf16_tail else None
+    if y is not None:
+        return y
     if not torch.is_grad_enabled() and fused._opt("enabled") and not bf16_tail \
             and fused._ctx_training_forward.get() == 0 \
             and all(t.dtype == torch.bfloat16 and t.is_cuda for t, _ in segments) \
