@@ -14,6 +14,7 @@ Drop-in surface (same names / signatures as the reference):
     hdbscan(points, min_cluster_size), embedding_track_candidates(...)   <- cuml.cluster.HDBSCAN (embedding validation)
     FusedAdamW(params, lr, ...), configure_optimizers(...), optimizer_step(...)   <- Trainer(gradient_clip_val) + AdamW(amsgrad) of every base
     knn_edges(idx, n_pts, sym), attention_weights(src, dst, graph, bn, weighting, ...)   <- DynamicGraphConstruction's edge list and weights
+    prepare_event_device(event, hparams), particle_hit_counts(pid), TrackMLDataset(..., device)   <- TrackMLDataset.__getitem__ (Modules/utils.py)
 
 Everything on the hot path runs in hand-written HIP kernels loaded from
 libhgnn_hip.so through the C ABI of include/hgnn_hip.h; there is no CPU or
@@ -38,5 +39,6 @@ from .edge_classifier import (weighted_bce_loss, weighted_bce_check, ec_training
 from .optim import FusedAdamW, configure_optimizers, optimizer_step  # noqa: F401
 from .ops import knn_edges  # noqa: F401
 from .graph_construction import attention_weights  # noqa: F401
+from .dataset import TrackMLDataset, prepare_event_device, particle_hit_counts  # noqa: F401
 
 __version__ = "0.1.0"

@@ -62,6 +62,11 @@ GA_FN_SIGMOID, GA_FN_EXP = 0, 1
 GA_TRAINING, GA_NORM = 1, 2
 GA_MEAN, GA_VAR, GA_RSTD, GA_SUMF, GA_E, GA_DBETA, GA_DGAMMA, GA_SGF = range(8)
 GA_STATE = 8
+# HGNN_EP_*: hgnn_event_*'s status bit, flag bits and device info vector
+EP_ST_BAD_ID = 1
+EP_NOISE, EP_REMOVE_ISOLATED, EP_USE_PRIMARY = 1, 2, 4
+EP_N_NODES, EP_E_EDGE_INDEX, EP_E_MODULEWISE, EP_E_SIGNAL, EP_STATUS = range(5)
+EP_INFO = 8
 
 class HgnnPlan(Structure):
     """mirror of ``struct hgnn_plan``"""
@@ -218,6 +223,19 @@ _SIGNATURES = {
                                              c_size_t, c_void_p]),
     "hgnn_graph_attention_backward": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hgnn_event_hit_counts_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
+    "hgnn_event_hit_counts": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
+    "hgnn_event_nodes_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
+    "hgnn_event_nodes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_double, c_int64, c_int32,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hgnn_event_inverse_mask": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "hgnn_event_edges_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
+    "hgnn_event_edges_count": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p]),
+    "hgnn_event_edges_fill": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                      c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hgnn_event_gather_rows": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -898,6 +898,72 @@ int hgnn_graph_attention_backward(const float* x, int64_t E, const float* bn_wei
                                   float* g_x, float* g_bn, void* workspace, size_t workspace_bytes,
                                   hgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Event preparation (reference Modules/utils.py:57-108, TrackMLDataset.__getitem__) on the device: the noise / pT /
+ * isolated-hit masks, nhits per particle, signal_mask, and the compaction and re-indexing of edge lists and node
+ * fields.  Added under ABI 26: additions only.  Every entry launches on `stream`, allocates nothing, never
+ * synchronises and reads nothing back; rocprim's scratch comes out of the caller's workspace (the size queries need the
+ * HIP runtime and a device, as hgnn_knn_edges_workspace_bytes does; their argument checks come first).  No float
+ * atomics: every output is a deterministic function of the inputs.  N < 2^31 and E < 2^31, else
+ * HGNN_ERR_INVALID_ARG; N = 0 or E = 0 is HGNN_OK with zero counts.  bool / flag arrays are one byte per element.
+ *
+ * hgnn_event_hit_counts: nhits[i] = the number of j with pid[j] == pid[i] (pid int64 [N], any values; 0 is a particle
+ *   like any other).  A stable radix sort of (pid, position) over all 64 key bits, run heads, run lengths, scattered
+ *   back.  With signal_mask != NULL also signal_mask[i] = nhits[i] >= n_hits && (primary == NULL || primary[i] == 1).
+ * hgnn_event_nodes: the node stage.  keep[i] =
+ *       (HGNN_EP_NOISE ? true : pid[i] != 0)
+ *    && (hard_ptcut > 0 ? pt[i] > (float)hard_ptcut : true)      the ORIGINAL pt, compared in float32; NaN fails
+ *    && (HGNN_EP_REMOVE_ISOLATED ? i occurs in edge_index [2, E] : true)
+ *   new_id int32 [N]: the exclusive scan of keep, -1 where not kept.  pt_out[i] = pid[i] == 0 ? 0 : pt[i].
+ *   nhits int64 [N] and signal_mask [N] as hgnn_event_hit_counts writes them (primary is read iff
+ *   HGNN_EP_USE_PRIMARY), both full length.  info device int64[HGNN_EP_INFO] is cleared first; then
+ *   info[HGNN_EP_N_NODES] = the number of kept hits, and info[HGNN_EP_STATUS] |= HGNN_EP_ST_BAD_ID when an id of
+ *   edge_index is outside [0, N) (read only with HGNN_EP_REMOVE_ISOLATED; such an id marks nothing and is never used
+ *   as an address).  edge_index may be NULL without HGNN_EP_REMOVE_ISOLATED.
+ * hgnn_event_inverse_mask: inverse_mask int64 [cap] = the kept positions ascending (inverse_mask[new_id[i]] = i for
+ *   every new_id[i] in [0, cap)).
+ * hgnn_event_edges_count: the edge stage of one list edges int64 [2, E].  Edge e = (a, b) is kept iff both ids are in
+ *   [0, N), new_id[a] >= 0, new_id[b] >= 0 and (edge_keep == NULL || edge_keep[e] != 0).  Writes *count (device
+ *   int64) = the number of kept edges and ORs HGNN_EP_ST_BAD_ID into *status (device int64, NOT cleared) when an id
+ *   of ANY edge of the list, kept or not, is outside [0, N); that edge is dropped and the id never used as an address.
+ *   The kept edges' positions (an exclusive scan: output order = input order) stay in the workspace for
+ *   hgnn_event_edges_fill, which must be given the same workspace, untouched, and the same edges / E / edge_keep /
+ *   new_id / N.  Another list can be filtered against the same new_id without redoing the node stage.
+ * hgnn_event_edges_fill: out int64 [2, cap] receives (new_id[a], new_id[b]) of every kept edge whose position is
+ *   < cap, and y_out[p] = y[e], y_pid_out[p] = y_pid[e] where those pointers are not NULL.
+ * hgnn_event_gather_rows: out[r, :] = src[index[r], :] for rows of `cols` elements of elem_bytes = 1, 4 or 8; a row
+ *   whose index is outside [0, n_rows) is zero-filled.  Needs no workspace.
+ * ------------------------------------------------------------------------ */
+#define HGNN_EP_ST_BAD_ID 1
+#define HGNN_EP_NOISE 1
+#define HGNN_EP_REMOVE_ISOLATED 2
+#define HGNN_EP_USE_PRIMARY 4
+#define HGNN_EP_N_NODES 0
+#define HGNN_EP_E_EDGE_INDEX 1
+#define HGNN_EP_E_MODULEWISE 2
+#define HGNN_EP_E_SIGNAL 3
+#define HGNN_EP_STATUS 4
+#define HGNN_EP_INFO 8
+int hgnn_event_hit_counts_workspace_bytes(int64_t N, size_t* bytes);
+int hgnn_event_hit_counts(const int64_t* pid, const int64_t* primary, int64_t N, int64_t n_hits, int64_t* nhits,
+                          uint8_t* signal_mask, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
+int hgnn_event_nodes_workspace_bytes(int64_t N, int64_t E, size_t* bytes);
+int hgnn_event_nodes(const int64_t* pid, const float* pt, const int64_t* primary, const int64_t* edge_index,
+                     int64_t N, int64_t E, double hard_ptcut, int64_t n_hits, int32_t flags, int32_t* new_id,
+                     float* pt_out, int64_t* nhits, uint8_t* signal_mask, int64_t* info, void* workspace,
+                     size_t workspace_bytes, hgnn_stream_t stream);
+int hgnn_event_inverse_mask(const int32_t* new_id, int64_t N, int64_t* inverse_mask, int64_t cap,
+                            hgnn_stream_t stream);
+int hgnn_event_edges_workspace_bytes(int64_t E, size_t* bytes);
+int hgnn_event_edges_count(const int64_t* edges, int64_t E, const uint8_t* edge_keep, const int32_t* new_id,
+                           int64_t N, int64_t* count, int64_t* status, void* workspace, size_t workspace_bytes,
+                           hgnn_stream_t stream);
+int hgnn_event_edges_fill(const int64_t* edges, int64_t E, const uint8_t* edge_keep, const int32_t* new_id, int64_t N,
+                          const uint8_t* y, const uint8_t* y_pid, int64_t* out, int64_t cap, uint8_t* y_out,
+                          uint8_t* y_pid_out, const void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
+int hgnn_event_gather_rows(const void* src, int64_t n_rows, int32_t cols, int32_t elem_bytes, const int64_t* index,
+                           int64_t n_out, void* out, hgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
