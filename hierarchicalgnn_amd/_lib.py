@@ -22,6 +22,7 @@ MLP_BWD_BLOCKS = 512   # HGNN_MLP_BWD_BLOCKS
 MLP_BWD_TILE_ROWS_N1024 = 32   # HGNN_MLP_BWD_TILE_ROWS_N1024: rows per tile of the N = 1024 backward layer
 GMM_STATE, GMM_BLOCKS = 16, 1024   # HGNN_GMM_STATE, HGNN_GMM_BLOCKS
 LN_ACT_BLOCKS = 1024   # HGNN_LN_ACT_BLOCKS
+MLP_BWD_F32_BLOCKS = 512   # HGNN_MLP_BWD_F32_BLOCKS: grid of the fp32 backward layer (device independent)
 RED_SUM, RED_MIN, RED_MAX = 0, 1, 2   # HGNN_RED_*
 DT_F32, DT_BF16, DT_I32, DT_I64, DT_F64 = 0, 1, 2, 3, 4   # HGNN_DT_*
 # HGNN_TE_*: entries of hgnn_track_eval's result vector
@@ -163,6 +164,9 @@ _SIGNATURES = {
     "hgnn_mlp_backward_layer_supported_bf16": (c_int, [c_int32, c_int32]),
     "hgnn_mlp_backward_layer_bf16": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hgnn_mlp_backward_layer_supported_f32": (c_int, [c_int32, c_int32]),
+    "hgnn_mlp_backward_layer_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hgnn_mlp_supported": (c_int, [POINTER(HgnnMlpDesc)]),
     "hgnn_mlp_forward_f32": (c_int, [POINTER(HgnnMlpDesc), c_void_p, c_void_p]),
     "hgnn_mlp_supported_f32_padded": (c_int, [POINTER(HgnnMlpDesc)]),

@@ -55,6 +55,43 @@ __device__ __forceinline__ float act_grad(float y, float a, int act) {
     }
 }
 
+// activation value and derivative from ONE evaluation of the transcendental part (act_apply + act_grad would
+// evaluate the erf polynomial / exp twice)
+__device__ __forceinline__ void act_val_grad(float y, int act, float& val, float& grad) {
+    switch (act) {
+        case HGNN_ACT_GELU: {
+            // Phi(y) = 0.5 (1 + erf(y / sqrt 2)) by Abramowitz-Stegun 7.1.26 (as fast_erf), whose exp(-(y/sqrt 2)^2)
+            // IS exp(-y^2 / 2), the Gaussian of the derivative's phi(y): one exp for both
+            const float ax = __builtin_fabsf(y) * 0.70710678118654752440f;
+            const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
+            float p = fmaf(1.061405429f, t, -1.453152027f);
+            p = fmaf(p, t, 1.421413741f);
+            p = fmaf(p, t, -0.284496736f);
+            p = fmaf(p, t, 0.254829592f);
+            p *= t;
+            const float e = __builtin_amdgcn_exp2f(-1.44269504088896341f * ax * ax);
+            const float erf_abs = fmaf(-p, e, 1.0f);
+            const float cdf = fmaf(0.5f, __builtin_copysignf(erf_abs, y), 0.5f);
+            val = y * cdf;
+            grad = fmaf(y, 0.3989422804014327f * e, cdf);
+            return;
+        }
+        case HGNN_ACT_TANH: {
+            const float t = fast_tanh(y);
+            val = t;
+            grad = fmaf(-t, t, 1.0f);
+            return;
+        }
+        case HGNN_ACT_RELU:
+            val = y > 0.f ? y : 0.f;
+            grad = y > 0.f ? 1.0f : 0.f;
+            return;
+        default:
+            val = y;
+            grad = 1.0f;
+    }
+}
+
 // Weight staging.  W[NF][Kdim] row-major (torch Linear.weight); chunk = columns [k0, k0+16).
 // One 1-KiB LDS-DMA piece covers 16 rows: lane (i = lane&15, g = lane>>4) fetches
 // W[16p+i][k0+4g .. +3] and the DMA lands it at lane*16 bytes, i.e. the piece is stored in exactly

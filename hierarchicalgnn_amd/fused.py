@@ -10,8 +10,9 @@ used whenever autograd is not recording: inference, and the first (no-grad) pass
 reentrant ``torch.utils.checkpoint`` segment -- which is how the reference runs all of its
 updates (Modules/gnn_utils.py:14-15).  When autograd records, the differentiable variant runs
 (``_FusedMLPTrain``: the same kernel dumping the pre-LayerNorm outputs, backward = HIP
-LayerNorm/activation row kernels + library GEMMs + segmented-reduce scatter); shapes it does not
-cover take the library path.
+LayerNorm/activation row kernels + library GEMMs + segmented-reduce scatter; with ``set_bwd_layer_f32`` the data
+gradients and the row passes of a layer boundary are one launch of ``hgnn_mlp_backward_layer_f32``); shapes it
+does not cover take the library path.
 """
 from __future__ import annotations
 
@@ -38,9 +39,10 @@ _enabled = True
 _train_enabled = True
 # library_calls: concat_mlp evaluated a Sequential with library GEMMs (no fused route); library_dgrad_calls: a data
 # gradient of the bf16 training backward went through a library GEMM; bwd_layer_calls: launches of the fused backward
-# layer; hybrid_train_calls: encoders under autograd on the fp32 first layer + bf16 tail (mlp.concat_mlp)
+# layer; hybrid_train_calls: encoders under autograd on the fp32 first layer + bf16 tail (mlp.concat_mlp);
+# bwd_layer_f32_calls: launches of the exact-fp32 fused backward layer (set_bwd_layer_f32)
 stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0, "library_calls": 0, "library_dgrad_calls": 0,
-         "bwd_layer_calls": 0, "hybrid_train_calls": 0}
+         "bwd_layer_calls": 0, "hybrid_train_calls": 0, "bwd_layer_f32_calls": 0}
 
 # Dispatch switches.  The module-level ``_name`` variables below are the PROCESS DEFAULTS (what the ``set_*`` functions
 # and the HGNN_* environment variables change).  ``options(...)`` overrides any of them for the current context only --
@@ -972,18 +974,32 @@ def _train_forward(ctx, route, indices, has_skip, tensors):
     return out, tables, skip, zs
 
 
+def _skip_segment(ctx, indices, tables, skip) -> int:
+    """the direct (un-gathered) segment that is the same tensor as the skip rows (``edges + MLP(..., edges)``) when both
+    need a gradient, or -1: the backward can then return the two gradients as one, added in a kernel's epilogue"""
+    n_seg = len(indices)
+    for s_i in range(n_seg):
+        t = tables[s_i]
+        if indices[s_i] is None and ctx.needs_input_grad[3 + s_i] and ctx.needs_input_grad[3 + n_seg] \
+                and t.data_ptr() == skip.data_ptr() and t.shape == skip.shape and t.stride() == skip.stride():
+            return s_i
+    return -1
+
+
 class _FusedMLPTrain(torch.autograd.Function):
     """Differentiable fused MLP.  Forward = the same MFMA kernel, additionally dumping each layer's
     pre-LayerNorm output z_l (``save_pre``).  Backward is written out by hand: LayerNorm / activation
     are re-derived from z_l with elementwise ATen kernels, data and weight gradients are library
-    GEMMs, and the gradients of gathered segments go back through the atomics-free segmented
-    reduce.  Compared with autograd through the unfused path this skips the second forward's GEMMs,
+    GEMMs (data gradients: the fused fp32 backward layer with ``set_bwd_layer_f32``), and the gradients of
+    gathered segments go back through the atomics-free segmented reduce.
+    Compared with autograd through the unfused path this skips the second forward's GEMMs,
     the [M,3L] concat and the gathered copies; with 288 GB of HBM the reference's checkpointing can
     also be switched off (hparams["checkpointing"]=False) and the dumps kept instead."""
 
     @staticmethod
     def forward(ctx, route, indices, has_skip, *tensors):
-        out, _, _, zs = _train_forward(ctx, route, indices, has_skip, tensors)
+        out, tables, skip, zs = _train_forward(ctx, route, indices, has_skip, tensors)
+        ctx.skip_seg = _skip_segment(ctx, indices, tables, skip) if has_skip else -1
         if route.head:
             # the hidden rows feeding the plain last Linear: one LayerNorm / activation row pass over the last dump
             ln = route.layers[ctx.n - 1][1]
@@ -1014,11 +1030,17 @@ class _FusedMLPTrain(torch.autograd.Function):
         aten = torch.ops.aten
         g = grad_out.contiguous()
         hip_rows = all(int(z.shape[1]) in (64, 128, 256, 512, 1024) for z in zs)
+        # set_bwd_layer_f32: the exact route's data gradients on hgnn_mlp_backward_layer_f32 (the opt-in split-bf16
+        # training route keeps precedence).  fuse[l]: dz_l . W_l, the LayerNorm / activation backward of layer l - 1 and
+        # its recomputed activations are ONE launch
+        f32_layer = hip_rows and _bwd_layer_f32_on and not _split3(ctx.net, train=True) and g.dtype == torch.float32
+        fuse = [bool(f32_layer and l > 0 and _bwd_layer_f32_supported(int(W[l].shape[0]), int(W[l].shape[1])))
+                for l in range(n)]
         ys, means, rstds, outs = [], [], [], []
         if hip_rows:
             # hidden activations a_l = act(LN(z_l)) for the weight gradients: one HIP pass per layer
-            outs = [_ln_act_forward(zs[l], lnw[l], lnb[l], ctx.acts[l], ctx.eps) if l < n - 1 else None
-                    for l in range(n)]
+            outs = [_ln_act_forward(zs[l], lnw[l], lnb[l], ctx.acts[l], ctx.eps) if l < n - 1 and not fuse[l + 1]
+                    else None for l in range(n)]
         else:
             # re-derive y_l = LN(z_l) (+ statistics) and a_l = act(y_l) with ATen elementwise kernels
             for l in range(n):
@@ -1035,9 +1057,15 @@ class _FusedMLPTrain(torch.autograd.Function):
         grads_params = [None] * (4 * n)
         grads_tables = [None] * n_seg
         da = g
+        below = None          # (dz, dgamma, dbeta, dbias) of layer l, when the fused layer of l + 1 has produced them
+        folded_skip = False
         for l in range(n - 1, -1, -1):
             code = ctx.acts[l]
-            if hip_rows:
+            if below is not None:
+                dz, dlw, dlb, dbias = below
+                below = None
+                grads_params[4 * l + 1] = dbias
+            elif hip_rows:
                 # act' -> LayerNorm backward -> dgamma / dbeta / dbias in ONE pass over (z_l, da)
                 dz, dlw, dlb, dbias = _ln_act_backward(zs[l], da, lnw[l], lnb[l], code, ctx.eps)
                 grads_params[4 * l + 1] = dbias
@@ -1056,7 +1084,13 @@ class _FusedMLPTrain(torch.autograd.Function):
                 grads_params[4 * l + 1] = dz.sum(dim=0)
             grads_params[4 * l + 2] = dlw
             grads_params[4 * l + 3] = dlb
-            if l > 0:
+            if l > 0 and fuse[l]:
+                dz_prev, a_prev, dlw_p, dlb_p, dbias_p = _bwd_layer_f32(
+                    dz, W[l], zs[l - 1], lnw[l - 1], lnb[l - 1], ctx.acts[l - 1], ctx.eps, want_a=True, weight=lw[l])
+                grads_params[4 * l] = _atb(dz, a_prev, ctx.net)
+                del a_prev
+                below = (dz_prev, dlw_p, dlb_p, dbias_p)
+            elif l > 0:
                 grads_params[4 * l] = _atb(dz, outs[l - 1], ctx.net)
                 da = _split3_linear(dz, lw[l], None, ctx.net)
                 if da is None:
@@ -1081,16 +1115,29 @@ class _FusedMLPTrain(torch.autograd.Function):
                         S = _seg_reduce(get_plan(idx, int(tab.shape[0])), dz, None, None)
                         dW_cols.append(_atb(S, tab, ctx.net))
                         if ctx.needs_input_grad[3 + s_i]:
-                            grads_tables[s_i] = S @ W_s
+                            if f32_layer and int(S.shape[0]) and _bwd_layer_f32_supported(int(W_s.shape[0]), w_s):
+                                grads_tables[s_i] = _bwd_layer_f32(S, W_s, None, None, None, 0, ctx.eps, weight=lw[0],
+                                                                   cols=(col, col + w_s))[0]
+                            else:
+                                grads_tables[s_i] = S @ W_s
                         del S
                     else:
                         dW_cols.append(_atb(dz, tab, ctx.net))
                         if ctx.needs_input_grad[3 + s_i]:
-                            gt = _split3_linear(dz, lw[0], (col, col + w_s), ctx.net)
-                            grads_tables[s_i] = gt if gt is not None else dz @ W_s
+                            if f32_layer and _bwd_layer_f32_supported(int(W_s.shape[0]), w_s):
+                                # edges + MLP(..., edges): the skip connection's gradient is added in the epilogue and
+                                # returned once, as this segment's (other direct segments leave folded_skip alone)
+                                fold = ctx.skip_seg == s_i
+                                grads_tables[s_i] = _bwd_layer_f32(dz, W_s, None, None, None, 0, ctx.eps,
+                                                                   skip=g if fold else None, weight=lw[0],
+                                                                   cols=(col, col + w_s))[0]
+                                folded_skip = folded_skip or fold
+                            else:
+                                gt = _split3_linear(dz, lw[0], (col, col + w_s), ctx.net)
+                                grads_tables[s_i] = gt if gt is not None else dz @ W_s
                     col += w_s
                 grads_params[0] = dW_cols[0] if n_seg == 1 else torch.cat(dW_cols, dim=1)
-        grad_skip = [g] if ctx.has_skip else []
+        grad_skip = [None if folded_skip else g] if ctx.has_skip else []
         return (None, None, None, *grads_tables, *grad_skip, *grads_params)
 
 
@@ -1165,6 +1212,83 @@ def _seg_reduce_wide(plan, dz):
     if F <= 512:
         return _seg_reduce(plan, dz, None, None)
     return torch.cat([_seg_reduce(plan, dz[:, c:c + 512].contiguous(), None, None) for c in range(0, F, 512)], dim=1)
+
+
+# the fused backward layer of the EXACT fp32 route (hgnn_mlp_backward_layer_f32, csrc/mlp_bwd_f32.hip).  OFF: whether it
+# beats the library GEMM + two HIP row passes is for tools/bench_bwd_layer.py --f32 to decide
+_bwd_layer_f32_on = os.environ.get("HGNN_BWD_LAYER_F32", "0") == "1"
+
+
+def set_bwd_layer_f32(flag: bool) -> None:
+    """process default (the backward runs on autograd's thread, which no ``options`` context reaches): the exact fp32
+    training backward forms its data gradients with ``hgnn_mlp_backward_layer_f32`` instead of library GEMMs + row
+    passes, wherever the shape is supported (HGNN_BWD_LAYER_F32=1)"""
+    global _bwd_layer_f32_on
+    _bwd_layer_f32_on = bool(flag)
+
+
+def _bwd_layer_f32_supported(K: int, N: int) -> bool:
+    """the exact fp32 training backward routes this boundary to the fused fp32 backward layer"""
+    if not _bwd_layer_f32_on:
+        return False
+    return bool(_lib.load().hgnn_mlp_backward_layer_supported_f32(int(K), int(N)))
+
+
+def _transposed_weight_f32(W, weight, cols):
+    """W^T [N, K] row-major fp32 of W = weight[:, cols]; with the Parameter ``weight`` given the copy is cached per
+    weight object and version (``_cached``), otherwise made from ``W`` itself"""
+    if weight is None:
+        return W.detach().float().t().contiguous()
+
+    def make():
+        Wd = weight.detach().float()
+        if cols is not None:
+            Wd = Wd[:, cols[0]:cols[1]]
+        return Wd.t().contiguous()
+    return _cached(weight, ("bwd_layer_f32", None if cols is None else tuple(cols)), make)
+
+
+def _aligned16(t):
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _bwd_layer_f32(dz, W, z_prev, gamma, beta, act, eps, skip=None, want_a=False, weight=None, cols=None):
+    """``hgnn_mlp_backward_layer_f32``.  W: the Linear's fp32 weight [K, N] (or a column slice of it); ``weight`` /
+    ``cols``: the Parameter W comes from and the column range taken, which let the W^T copy live in the weight cache.
+    LayerNorm form (z_prev given): returns (dz_prev, a_prev or None, dgamma, dbeta, dbias); input form: (dx,)."""
+    if not (dz.is_cuda and W.is_cuda):
+        raise RuntimeError("_bwd_layer_f32 needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
+    if dz.dtype != torch.float32 or (z_prev is not None and z_prev.dtype != torch.float32) \
+            or (skip is not None and skip.dtype != torch.float32):
+        raise RuntimeError("_bwd_layer_f32: float32 rows only")
+    M, K = int(dz.shape[0]), int(dz.shape[1])
+    N = int(W.shape[1])
+    dev = dz.device
+    ln = z_prev is not None
+    if M == 0:      # nothing to launch (an empty tensor has no address to tell the two forms apart by)
+        zero = torch.zeros((0, N), dtype=torch.float32, device=dev)
+        sums = torch.zeros((3, N), dtype=torch.float32, device=dev)
+        return (zero, zero.clone() if want_a else None, sums[0], sums[1], sums[2]) if ln else (zero,)
+    wt = _transposed_weight_f32(W, weight, cols)
+    out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    a_prev = torch.empty((M, N), dtype=torch.float32, device=dev) if (ln and want_a) else None
+    partials = torch.empty((_lib.MLP_BWD_F32_BLOCKS, 3, N), dtype=torch.float32, device=dev) if ln else None
+    # the kernel reads 16-byte pieces: a view that starts off that grid (a slice of a flattened parameter buffer) is copied
+    gm = _aligned16(gamma.detach().float().contiguous()) if ln else None
+    bt = _aligned16(beta.detach().float().contiguous()) if ln else None
+    zp = _aligned16(z_prev.contiguous()) if ln else None
+    sk = _aligned16(skip.contiguous()) if skip is not None else None
+    dzc = _aligned16(dz.contiguous())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().hgnn_mlp_backward_layer_f32(
+            _lib.ptr(dzc), M, K, N, _lib.ptr(wt), _lib.ptr(zp), _lib.ptr(gm), _lib.ptr(bt), int(act),
+            float(eps), _lib.ptr(sk), _lib.ptr(out), _lib.ptr(a_prev), _lib.ptr(partials),
+            _lib.current_stream(dev)), "hgnn_mlp_backward_layer_f32")
+    stats["bwd_layer_f32_calls"] += 1
+    if not ln:
+        return (out,)
+    sums = partials.sum(dim=0)
+    return out, a_prev, sums[0], sums[1], sums[2]
 
 
 class _FusedMLPTrainBf16(torch.autograd.Function):

@@ -469,7 +469,8 @@ int hgnn_project_f32_split3(const float* x, int64_t M, int32_t K, const void* w_
 
 /* LayerNorm + activation of one make_mlp layer (Modules/utils.py:169-196: Linear -> LayerNorm ->
  * act) over rows z[M, W] (the Linear's output, as dumped by hgnn_mlp_forward_f32's save_pre), one
- * pass each -- the elementwise half of the fused MLP's backward (the GEMM half is the library's):
+ * pass each -- the elementwise half of the fused MLP's backward (the GEMM half is the library's, or both halves in one
+ * launch: hgnn_mlp_backward_layer_f32 below):
  *   forward :  out[r]    = act(gamma * (z[r] - mean_r) * rstd_r + beta)
  *   backward:  grad_z[r] = d/dz of the above applied to grad_out[r]; and per-workgroup column sums
  *              partials[b][0][c] = sum_r grad_y * xhat (dgamma), [b][1][c] = sum_r grad_y (dbeta),
@@ -533,6 +534,27 @@ int hgnn_mlp_backward_layer_supported_bf16(int32_t K, int32_t N);
 int hgnn_mlp_backward_layer_bf16(const void* dz, int64_t M, int32_t K, int32_t N, const void* Wt_frag,
                                  const void* z_prev, const float* ln_w, const float* ln_b, int32_t act, float eps,
                                  const void* skip, void* out, void* a_prev, float* partials, hgnn_stream_t stream);
+
+/* hgnn_mlp_backward_layer_f32: the same fused backward layer for the EXACT fp32 training path, fp32 rows throughout, on
+ * the fp32 matrix instruction (v_mfma_f32_16x16x4_f32: a chain of fused multiply-adds, as hgnn_mlp_forward_f32):
+ *   z_prev != NULL ("LayerNorm form"):  da = dz[M,K] . W[K,N];  out = dz' = dLayerNorm(act'(LN(z_prev)) * da);  a_prev
+ *       (optional) receives act(LN(z_prev)); partials: float [HGNN_MLP_BWD_F32_BLOCKS][3][N] per-workgroup column sums
+ *       of dgamma, dbeta and dz' (the previous Linear's bias gradient) -- the three sums of hgnn_ln_act_backward_f32;
+ *       the caller adds the partial rows, idle workgroups write zeros.  ln_w, ln_b and partials are required, skip
+ *       must be NULL.  M = 0 writes zero partials.
+ *   z_prev == NULL ("input form"):      out = dz . W (+ skip), skip [M,N] or NULL; a_prev and partials must be NULL.
+ * Wt: W^T, i.e. the [N][K] matrix Wt[n][k] = W[k][n], plain row-major fp32 (row stride K).  dz [M,K], z_prev / skip /
+ * out / a_prev [M,N] row-major; every pointer 16-byte aligned.  K a multiple of 16 with 64 <= K <= 1024, N in
+ * {64, 128, 256, 512} (anything else: HGNN_ERR_UNSUPPORTED, nothing written); act = HGNN_ACT_*, exact-erf GELU.
+ * LayerNorm statistics are centred (mean first, then sum((z - mean)^2)).  One wave owns 16 rows and all N features;
+ * workgroups walk the 64-row tiles in a fixed order on a grid that does not depend on the device, the column sums are
+ * combined in a fixed order without atomics: the same inputs give the same bits everywhere. */
+#define HGNN_MLP_BWD_F32_BLOCKS 512
+int hgnn_mlp_backward_layer_supported_f32(int32_t K, int32_t N);
+int hgnn_mlp_backward_layer_f32(const float* dz, int64_t M, int32_t K, int32_t N, const float* Wt,
+                                const float* z_prev, const float* ln_w, const float* ln_b, int32_t act, float eps,
+                                const float* skip, float* out, float* a_prev,
+                                float* partials /* [HGNN_MLP_BWD_F32_BLOCKS][3][N] */, hgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Tracking-performance metrics (reference Modules/tracking_utils.py:18-83, eval_metrics, cupy / cupy.sparse
