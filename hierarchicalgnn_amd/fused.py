@@ -40,7 +40,8 @@ _train_enabled = True
 # library_calls: concat_mlp evaluated a Sequential with library GEMMs (no fused route); library_dgrad_calls: a data
 # gradient of the bf16 training backward went through a library GEMM; bwd_layer_calls: launches of the fused backward
 # layer; hybrid_train_calls: encoders under autograd on the fp32 first layer + bf16 tail (mlp.concat_mlp);
-# bwd_layer_f32_calls: launches of the exact-fp32 fused backward layer (set_bwd_layer_f32)
+# bwd_layer_f32_calls: launches of the exact-fp32 fused backward layer (set_bwd_layer_f32).  Created on first use:
+# split3_wgrad_calls / wgrad_f32_calls / library_wgrad_calls, the branch ``_atb`` took for a weight gradient
 stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0, "library_calls": 0, "library_dgrad_calls": 0,
          "bwd_layer_calls": 0, "hybrid_train_calls": 0, "bwd_layer_f32_calls": 0}
 
@@ -910,7 +911,10 @@ def _ln_act_backward(z, grad_out, gamma, beta, act, eps):
 def _atb(A: torch.Tensor, B: torch.Tensor, net=None) -> torch.Tensor:
     """A^T B for tall A [n, p], B [n, q] with a small [p, q] result: a weight gradient.  With the split-bf16 mode on
     (``net`` given) and fp32 operands of at least 4096 rows: the hand-written split-K kernel on the bf16 matrix pipe
-    (ops.wgrad_f32_split3: ~1.7 ms where the library paths below need 3.6-4 ms at n = 2M).  Otherwise: the library picks
+    (ops.wgrad_f32_split3: ~1.7 ms where the library paths below need 3.6-4 ms at n = 2M).  With ``set_wgrad_f32`` and
+    fp32 device operands whose widths are multiples of 8 up to 1024: the exact fp32-MFMA split-K kernel (ops.wgrad_f32:
+    fixed order, the same bits on every device; 4.05 against 3.59 ms at n = 2M, profiles/wgrad_f32.json).  Otherwise
+    (``stats["library_wgrad_calls"]``): the library picks
     a small output tile without split-K for these (p*q/1024 workgroups walking all n rows: 1.2 ms for the
     8 GFLOP of n = 120k, ~110 TFLOP/s at n = 2M); a batched product over row blocks plus one sum fills the
     chip (fixed summation order: deterministic).  EC-IN training step 368 -> 306 ms."""
@@ -920,6 +924,14 @@ def _atb(A: torch.Tensor, B: torch.Tensor, net=None) -> torch.Tensor:
         from .ops import wgrad_f32_split3
         stats["split3_wgrad_calls"] = stats.get("split3_wgrad_calls", 0) + 1
         return wgrad_f32_split3(A, B)
+    # set_wgrad_f32: the exact route's weight gradients on hgnn_wgrad_f32 (fp32 MFMA, fixed order) instead of the library
+    if _wgrad_f32_on and n >= 1 and A.dtype == torch.float32 and B.dtype == torch.float32 and A.is_cuda and B.is_cuda \
+            and int(A.shape[1]) % 8 == 0 and int(B.shape[1]) % 8 == 0 \
+            and 0 < int(A.shape[1]) <= 1024 and 0 < int(B.shape[1]) <= 1024:
+        from .ops import wgrad_f32
+        stats["wgrad_f32_calls"] = stats.get("wgrad_f32_calls", 0) + 1
+        return wgrad_f32(A, B)
+    stats["library_wgrad_calls"] = stats.get("library_wgrad_calls", 0) + 1
     chunks = max(16, min(256, n // 8192))   # 4096 / 8192 rows per block measured equal, 32768 6 % slower
     c = n // chunks
     if c < 256:
@@ -1225,6 +1237,20 @@ def set_bwd_layer_f32(flag: bool) -> None:
     passes, wherever the shape is supported (HGNN_BWD_LAYER_F32=1)"""
     global _bwd_layer_f32_on
     _bwd_layer_f32_on = bool(flag)
+
+
+# the weight gradients of the EXACT fp32 route on hgnn_wgrad_f32 (csrc/wgrad_f32.hip) instead of the library's GEMMs.
+# OFF: the default is decided by tools/bench_wgrad_f32.py and the 3 x spread rule (DESIGN.md section 3)
+_wgrad_f32_on = os.environ.get("HGNN_WGRAD_F32", "0") == "1"
+
+
+def set_wgrad_f32(flag: bool) -> None:
+    """process default (the backward runs on autograd's thread, which no ``options`` context reaches): ``_atb`` -- every
+    weight gradient dz^T a of the exact fp32 training backward, the N-row S^T table of gathered segments included --
+    takes ``hgnn_wgrad_f32`` wherever both widths are multiples of 8 up to 1024 (HGNN_WGRAD_F32=1).  The opt-in
+    split-bf16 route keeps precedence; independent of ``set_bwd_layer_f32``."""
+    global _wgrad_f32_on
+    _wgrad_f32_on = bool(flag)
 
 
 def _bwd_layer_f32_supported(K: int, N: int) -> bool:

@@ -684,3 +684,32 @@ def wgrad_f32_split3(dz: torch.Tensor, rows: torch.Tensor, out: Optional[torch.T
                                              _lib.ptr(ws), ws.numel(), _lib.current_stream(dz.device)),
                    "hgnn_wgrad_f32_split3")
     return out
+
+
+def wgrad_f32(dz: torch.Tensor, rows: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``dz^T @ rows`` for FP32 ``dz[M, Ho]`` and ``rows[M, Hi]`` in EXACT fp32 (``hgnn_wgrad_f32``: every product
+    formed once from the fp32 operands on the fp32 MFMA, split-K in a fixed order, no atomics -- the same bits on every
+    device and in every run): the weight gradients of the default fp32 training backward.  Widths: multiples of 8 up
+    to 1024.  Same conventions as :func:`wgrad_f32_split3`, without ``colsum``."""
+    _require_hip(dz, "dz")
+    _require_hip(rows, "rows")
+    if dz.dtype != torch.float32 or rows.dtype != torch.float32 or dz.dim() != 2 or rows.dim() != 2 \
+            or dz.shape[0] != rows.shape[0]:
+        raise RuntimeError("wgrad_f32: fp32 dz[M, Ho] and rows[M, Hi] expected")
+    dz, rows = _wgrad_operand(dz), _wgrad_operand(rows)
+    M, Ho, Hi = int(dz.shape[0]), int(dz.shape[1]), int(rows.shape[1])
+    if out is None:
+        out = torch.empty((Ho, Hi), dtype=torch.float32, device=dz.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (Ho, Hi) or out.stride(1) != 1:
+        raise RuntimeError("wgrad_f32: out must be fp32 [Ho, Hi] with unit column stride")
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(lib.hgnn_wgrad_f32_workspace_bytes(M, Ho, Hi, ctypes.byref(nbytes)), "hgnn_wgrad_f32_workspace_bytes")
+    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dz.device)
+    lda = int(dz.stride(0)) if M > 1 else Ho
+    ldb = int(rows.stride(0)) if M > 1 else Hi
+    with torch.cuda.device(dz.device):
+        _lib.check(lib.hgnn_wgrad_f32(_lib.ptr(dz), lda, _lib.ptr(rows), ldb, M, Ho, Hi,
+                                      ctypes.c_void_p(out.data_ptr()), int(out.stride(0)),
+                                      _lib.ptr(ws), ws.numel(), _lib.current_stream(dz.device)), "hgnn_wgrad_f32")
+    return out

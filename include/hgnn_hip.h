@@ -53,7 +53,7 @@ extern "C" {
 /* hgnn_assign_match and hgnn_assign_match_workspace_bytes were added without a bump: they are additions, and
  * no existing entry point, struct or constant changed layout or meaning.  The same holds for
  * hgnn_segment_reduce_f32_ex, hgnn_plan_item_order(_workspace_bytes), hgnn_get_option and the optimiser step
- * (hgnn_optim_*, hgnn_sizeof_opt_entry, struct hgnn_opt_entry, HGNN_OPT_*). */
+ * (hgnn_optim_*, hgnn_sizeof_opt_entry, struct hgnn_opt_entry, HGNN_OPT_*) and for hgnn_wgrad_f32(_workspace_bytes). */
 #define HGNN_ABI_VERSION 26
 
 typedef void* hgnn_stream_t; /* hipStream_t */
@@ -514,6 +514,23 @@ int hgnn_wgrad_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, int6
 int hgnn_wgrad_f32_split3(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int32_t Ho, int32_t Hi,
                           float* out, int64_t ldo, float* colsum, void* workspace, size_t workspace_bytes,
                           hgnn_stream_t stream);
+
+/* hgnn_wgrad_f32: the EXACT weight gradient of the fp32 training backward (additions under ABI 26, as above):
+ *   out[ho, hi] = sum_m A[m, ho] * B[m, hi]   with A = dz [M, Ho], B = the layer's input rows [M, Hi], fp32 row-major,
+ *   row strides lda / ldb in floats (multiples of 4 that cover the columns; rows 16-byte aligned, so a column slice of
+ *   a wider matrix can be passed in place); out fp32 [Ho, ldo], ldo >= Hi.  Ho, Hi: positive multiples of 8, <= 1024.
+ *   Every product is formed once from the fp32 operands by v_mfma_f32_16x16x4_f32 (no split, no reduced-precision
+ *   plane).  Order contract: split-K over the rows; inside a slice every output element is the chain
+ *   acc = fmaf(A[m, ho], B[m, hi], acc) over the slice's rows in order; the slices' partials are added in slice order
+ *   by four chains (slices k = 0, 1, 2, 3 mod 4; the remainder joins chain 0) combined as (s0 + s1) + (s2 + s3).  No
+ *   atomics.  Slices, rows per slice and tile are a pure function of (M, Ho, Hi) -- never of the device -- so the same
+ *   inputs give the same bits on every device and in every run.  M == 0 writes zeros to out and launches nothing else.
+ *   No column sums (the fp32 route's bias gradient comes from hgnn_ln_act_backward_f32 / the fp32 backward layer).
+ *   workspace: device memory of hgnn_wgrad_f32_workspace_bytes(M, Ho, Hi) bytes, 16-byte aligned.  Every refusal
+ *   (HGNN_ERR_INVALID_ARG + hgnn_last_error) is decided before any HIP call and touches no pointer. */
+int hgnn_wgrad_f32_workspace_bytes(int64_t M, int32_t Ho, int32_t Hi, size_t* bytes);
+int hgnn_wgrad_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int32_t Ho, int32_t Hi,
+                   float* out, int64_t ldo, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
 
 /* hgnn_mlp_backward_layer_bf16: the hand-written DATA gradient of one Linear of the bf16 training path, fused with
  * what follows it in the backward:
