@@ -180,6 +180,8 @@ _SIGNATURES = {
     "hgnn_mlp_forward_bf16_split": (c_int, [POINTER(HgnnMlpDesc), c_void_p, c_void_p]),
     "hgnn_mlp_supported_f32_split3": (c_int, [POINTER(HgnnMlpDesc)]),
     "hgnn_mlp_forward_f32_split3": (c_int, [POINTER(HgnnMlpDesc), c_void_p, c_void_p]),
+    "hgnn_mlp_supported_f32_split3_padded": (c_int, [POINTER(HgnnMlpDesc)]),
+    "hgnn_mlp_forward_f32_split3_padded": (c_int, [POINTER(HgnnMlpDesc), c_void_p, c_void_p]),
     "hgnn_linear_f32_split3": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "hgnn_project_f32_split3": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                         c_void_p]),

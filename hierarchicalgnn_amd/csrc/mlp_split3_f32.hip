@@ -55,6 +55,14 @@ struct Args {
 #endif
 };
 
+// the PAD kernels' argument (hgnn_mlp_forward_f32_split3_padded): a struct of its own, so that the kernel argument of
+// every native kernel -- and with it the offsets of the implicit arguments behind it -- stays what it was
+struct ArgsPad : Args {
+    int real[3];          // real output width of every layer (<= its stored width; the rest is zero padding)
+};
+template <bool PAD>
+using ArgsOf = std::conditional_t<PAD, ArgsPad, Args>;
+
 // phase boundaries of a tile, stamped by lane 0 of every wave in the diagnostic build only (no stamp executes in the
 // product build): 0 tile start | 1 projected rows added | 2 first panel stored | 3 layer-1 GEMM done | 4 LayerNorm + GELU done
 // | 5 hidden planes written | 6 output GEMM done | 7 output LayerNorm + tanh done | 8 rows stored
@@ -150,6 +158,103 @@ __device__ __forceinline__ void layernorm_act(f32x4 (&acc)[NT][NJ], const float*
             c = fmaf(d, d, c);
         }
         const float var = fmaf(c, (float)(NT * 16), q) * inv_n;
+        rstd[j] = 1.0f / sqrtf(var + eps);
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const f32x4 w4 = *(const f32x4*)(lnw + t * 16);
+        const f32x4 b4 = *(const f32x4*)(lnb + t * 16);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            f32x4 v = acc[t][j];
+            v.x = act_apply(fmaf((v.x - mean[j]) * rstd[j], w4.x, b4.x), act);
+            v.y = act_apply(fmaf((v.y - mean[j]) * rstd[j], w4.y, b4.y), act);
+            v.z = act_apply(fmaf((v.z - mean[j]) * rstd[j], w4.z, b4.z), act);
+            v.w = act_apply(fmaf((v.w - mean[j]) * rstd[j], w4.w, b4.w), act);
+            acc[t][j] = v;
+        }
+    }
+}
+
+// PAD kernels (widths between the grid's, hgnn_mlp_forward_f32_split3_padded): only the first n_real of the layer's
+// NW * NT * 16 stored features are real (n_real % 4 == 0: a lane's four features of a tile are all real or all padding).
+// Wave w holds n_w = clamp(n_real - w NT 16, 0, NT 16) of them -- possibly none -- so the waves' pairs are pooled with
+// their COUNTS:   mean = sum n_w m_w / n,   M2 = sum M2_w + sum n_w (m_w - mean)^2,   var = M2 / n     (n = n_real).
+// Padded quads are selected out of both passes; true divisions (1 / n is rounded where n is no power of two: a constant
+// row must keep deviations of exactly 0).  With nothing padded every n_w is the power of two NT 16 and each value
+// below equals layernorm_act's bit for bit (scaling by a power of two commutes with every rounding in the chains).
+// Padded features have ln_w = ln_b = 0: they come out as 0 and feed zero planes into the next layer.
+template <int NT, int NW, int ACT>
+__device__ __forceinline__ void layernorm_act_pad(f32x4 (&acc)[NT][NJ], const float* __restrict__ lnw,
+                                                  const float* __restrict__ lnb, int act_rt, float eps, float* red,
+                                                  int wave, int ei, int g, int n_real) {
+    const int act = ACT >= 0 ? ACT : act_rt;
+    constexpr int S = NT * 16;
+    auto count = [&](int w) {
+        const int n = n_real - w * S;
+        return n < 0 ? 0 : (n > S ? S : n);
+    };
+    const int nw = count(wave);
+    const float nwf = (float)nw;
+    bool real[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) real[t] = t * 16 + 4 * g < nw;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        float s = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const f32x4 v = acc[t][j];
+            const float p = (v.x + v.y) + (v.z + v.w);
+            s += real[t] ? p : 0.f;
+        }
+        s += __shfl_xor(s, 16);
+        s += __shfl_xor(s, 32);
+        const float m = nw > 0 ? s / nwf : 0.f;
+        float q = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const f32x4 v = acc[t][j];
+            const float dx = v.x - m, dy = v.y - m, dz = v.z - m, dw = v.w - m;
+            float qn = fmaf(dx, dx, q);
+            qn = fmaf(dy, dy, qn);
+            qn = fmaf(dz, dz, qn);
+            qn = fmaf(dw, dw, qn);
+            q = real[t] ? qn : q;
+        }
+        q += __shfl_xor(q, 16);
+        q += __shfl_xor(q, 32);
+        if (g == 0) {
+            f32x2 sq;
+            sq.x = m;
+            sq.y = q;
+            *(f32x2*)(red + (wave * TE + j * 16 + ei) * 2) = sq;
+        }
+    }
+    __syncthreads();
+    const float nf = (float)n_real;
+    float cnt[NW];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) cnt[w] = (float)count(w);
+    float rstd[NJ], mean[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        float mw[NW], s = 0.f, q = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const f32x2 sq = *(const f32x2*)(red + (w * TE + j * 16 + ei) * 2);
+            mw[w] = sq.x;
+            s += cnt[w] * sq.x;
+            q += sq.y;
+        }
+        mean[j] = s / nf;
+        float c = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float d = mw[w] - mean[j];
+            c = fmaf(cnt[w] * d, d, c);
+        }
+        const float var = (c + q) / nf;
         rstd[j] = 1.0f / sqrtf(var + eps);
     }
 #pragma unroll
@@ -268,8 +373,13 @@ __device__ __forceinline__ void gemm3s(f32x4 (&acc)[NT][NJ], const u16x8* __rest
 // NW waves share the 64 rows (8: two per SIMD; 16: four per SIMD -- at latent 256 the two bf16 planes of the hidden
 // rows leave room for ONE workgroup per CU, whose waves are phase-locked by the barriers: more of them hide more
 // latency); NTH / NTO: 16-feature tiles per wave of the hidden / output layers; NL = 2 or 3 layers
-template <int NW, int NTH, int NTO, int NL, int ACT_H, int ACT_O>
-__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_mlp_f32_split3(const Args a) {
+// PAD (hgnn_mlp_forward_f32_split3_padded): the real widths a.real[l] may be below the stored H / O (parameters zero
+// padded, W[l >= 1] also in its columns) and a segment may end inside a 128-wide panel (its column block of W[0] zero
+// padded to whole panels): pieces past a segment's width are not loaded and stored as zeros, statistics are pooled
+// with the waves' real counts (layernorm_act_pad), skip / out rows have the real width.  No dumps.  false for every
+// kernel of the native shapes, whose device code does not depend on it.
+template <int NW, int NTH, int NTO, int NL, int ACT_H, int ACT_O, bool PAD = false>
+__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_mlp_f32_split3(const ArgsOf<PAD> a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NTHR = NW * 64;
     constexpr int H = NTH * NW * 16;
@@ -319,9 +429,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_mlp_f32_split3(con
     // ---- input panels: 16 rows per pass with 8 waves
     constexpr int RPP = NTHR / LPR;
     constexpr int NP = TE / RPP;
+    // PAD: a segment w wide occupies ceil(w / 128) panels; a.K1 counts the stored (padded) columns of W[0]
     const int np = a.K1 / PK;
-    const int p1 = a.seg_width[0] / PK;
-    const int p2 = p1 + (a.n_seg > 1 ? a.seg_width[1] / PK : np);
+    const int p1 = PAD ? (a.seg_width[0] + PK - 1) / PK : a.seg_width[0] / PK;
+    const int p2 = p1 + (a.n_seg > 1 ? (PAD ? (a.seg_width[1] + PK - 1) / PK : a.seg_width[1] / PK) : np);
     // pre-projected gathered segments (fp32 rows) by LDS-DMA, WAVE-PRIVATE: a wave fetches only its own 64-feature slice
     // (256 bytes) of the 16 rows of a pass into its own ring of four buffers, so the P phase needs no workgroup
     // barrier at all (the first version moved whole rows and paid one barrier per pass: 8 per tile in a workgroup whose
@@ -373,22 +484,38 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_mlp_f32_split3(con
             px[i] = a.seg_table[0] + (size_t)ti[i * RPP + prow] * (size_t)a.seg_width[0] + pcol * 4;
         f32x4 st[NP];
         int pl = 0;
+        int left = a.seg_width[0];   // PAD: columns of the current segment from this panel's first on
         auto load_panel = [&]() {
+            if constexpr (PAD) {
+                // a piece past the segment's width is NOT read (the table's last row ends the allocation): its address
+                // is replaced by the table's first 16 bytes, its value by zeros in both planes
+                const bool in = pcol * 4 < left;
 #pragma unroll
-            for (int i = 0; i < NP; ++i) {
-                st[i] = *(const f32x4*)px[i];
-                px[i] += PK;
+                for (int i = 0; i < NP; ++i) {
+                    const f32x4 v = *(const f32x4*)(in ? px[i] : a.seg_table[0]);
+                    st[i] = in ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+                    px[i] += PK;
+                }
+                left -= PK;
+            } else {
+#pragma unroll
+                for (int i = 0; i < NP; ++i) {
+                    st[i] = *(const f32x4*)px[i];
+                    px[i] += PK;
+                }
             }
             ++pl;
             if (pl == p1) {
 #pragma unroll
                 for (int i = 0; i < NP; ++i)
                     px[i] = a.seg_table[1] + (size_t)ti[TE + i * RPP + prow] * (size_t)a.seg_width[1] + pcol * 4;
+                if constexpr (PAD) left = a.seg_width[1];
             }
             if (pl == p2) {
 #pragma unroll
                 for (int i = 0; i < NP; ++i)
                     px[i] = a.seg_table[2] + (size_t)ti[2 * TE + i * RPP + prow] * (size_t)a.seg_width[2] + pcol * 4;
+                if constexpr (PAD) left = a.seg_width[2];
             }
         };
         auto store_panel = [&](int buf) {   // buffers 2 buf (hi) and 2 buf + 1 (mid)
@@ -449,9 +576,14 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_mlp_f32_split3(con
             }
         }
         HGNN_STAMP(3);
+        if constexpr (PAD) {
+            layernorm_act_pad<NTH, NW, ACT_H>(acc1, a.lnw[0] + wave * NTH * 16 + 4 * g, a.lnb[0] + wave * NTH * 16 + 4 * g,
+                                              a.act[0], a.eps, red, wave, ei, g, a.real[0]);
+        } else {
         dump_pre<NTH, H>(acc1, a.save_pre[0], a.M, e0, wave, ei, g);
         layernorm_act<NTH, NW, ACT_H>(acc1, a.lnw[0] + wave * NTH * 16 + 4 * g, a.lnb[0] + wave * NTH * 16 + 4 * g, a.act[0],
                                       a.eps, red, wave, ei, g);
+        }
         // (the barrier inside layernorm_act also means: every wave is done reading the panels)
         HGNN_STAMP(4);
         write_hidden2<NTH, HRS, PLB>(acc1, smem, wave, ei, g);
@@ -465,9 +597,15 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_mlp_f32_split3(con
                 const u16x8* wp1 = (const u16x8*)a.W[1] + (size_t)(wave * NTH) * 64 + lane;
                 gemm3s<NTH, HRS, NW>(acc1, wp1, 0, 2 * NC, hlane, hlane + PLB, NC);
             }
+            if constexpr (PAD) {
+                layernorm_act_pad<NTH, NW, ACT_H>(acc1, a.lnw[1] + wave * NTH * 16 + 4 * g,
+                                                  a.lnb[1] + wave * NTH * 16 + 4 * g, a.act[1], a.eps, red, wave, ei, g,
+                                                  a.real[1]);
+            } else {
             dump_pre<NTH, H>(acc1, a.save_pre[1], a.M, e0, wave, ei, g);
             layernorm_act<NTH, NW, ACT_H>(acc1, a.lnw[1] + wave * NTH * 16 + 4 * g, a.lnb[1] + wave * NTH * 16 + 4 * g,
                                           a.act[1], a.eps, red, wave, ei, g);
+            }
             write_hidden2<NTH, HRS, PLB>(acc1, smem, wave, ei, g);   // (barrier inside layernorm_act: all reads done)
             __syncthreads();
         }
@@ -487,21 +625,39 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_mlp_f32_split3(con
 #pragma unroll
         for (int k = 0; k < NIX; ++k)
             if (has_next && tid + k * NTHR < 5 * TE) ti_next[tid + k * NTHR] = r_next[k];
-        dump_pre<NTO, O>(acc2, a.save_pre[LO], a.M, e0, wave, ei, g);
+        if constexpr (!PAD) dump_pre<NTO, O>(acc2, a.save_pre[LO], a.M, e0, wave, ei, g);
         // skip rows BEFORE the next tile's DMAs: queued behind them they would wait for the projected rows
         f32x4 sk[NTO][NJ];
         size_t off[NJ];
         bool valid[NJ];
+        // PAD: rows of a.real[LO] floats; this lane's piece of tile t (four features: all real or all padding) exists
+        // where its first column is below the real width -- a piece that does not is neither read nor written
+        int o_real = O;
+        if constexpr (PAD) o_real = a.real[LO];
+        const int col0 = wave * NTO * 16 + 4 * g;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const long long e = e0 + j * 16 + ei;
             valid[j] = e < a.M;
+            if constexpr (PAD) {
+                off[j] = (size_t)(valid[j] ? e : a.M - 1) * (size_t)o_real + (size_t)col0;
+                if (a.skip != nullptr) {
+#pragma unroll
+                    for (int t = 0; t < NTO; ++t)
+                        sk[t][j] = *(const f32x4*)(a.skip + (col0 + t * 16 < o_real ? off[j] + t * 16 : (size_t)0));
+                }
+            } else {
             off[j] = (size_t)(valid[j] ? e : a.M - 1) * O + (size_t)(wave * NTO * 16 + 4 * g);
             if (a.skip != nullptr) {
 #pragma unroll
                 for (int t = 0; t < NTO; ++t) sk[t][j] = *(const f32x4*)(a.skip + off[j] + t * 16);
             }
+            }
         }
+        if constexpr (PAD)
+            layernorm_act_pad<NTO, NW, ACT_O>(acc2, a.lnw[LO] + wave * NTO * 16 + 4 * g, a.lnb[LO] + wave * NTO * 16 + 4 * g,
+                                              a.act[LO], a.eps, red, wave, ei, g, o_real);
+        else
         layernorm_act<NTO, NW, ACT_O>(acc2, a.lnw[LO] + wave * NTO * 16 + 4 * g, a.lnb[LO] + wave * NTO * 16 + 4 * g, a.act[LO],
                                       a.eps, red, wave, ei, g);
         // (the barrier inside: every wave is past the hidden planes, the next tile's indices are visible)
@@ -516,6 +672,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_mlp_f32_split3(con
             if (!valid[j]) continue;
 #pragma unroll
             for (int t = 0; t < NTO; ++t) {
+                if (PAD && col0 + t * 16 >= o_real) continue;
                 f32x4 v = acc2[t][j];
                 if (a.skip != nullptr) v += sk[t][j];
                 *(f32x4*)(a.out + off[j] + t * 16) = v;
@@ -671,8 +828,8 @@ int g_opt_split3_one_wg = 0;    // hgnn_set_option("mlp_split3_one_wg"): DIAGNOS
 int g_opt_split3_rows128 = 1;   // hgnn_set_option("mlp_split3_rows128"): 1 (default) the 128-row kernel for K -> 512 -> 256 at M >= 65,536 (two tiles per CU)
 static int g_cus = 0;
 
-template <int NW, int NTH, int NTO, int NL, int ACT_H, int ACT_O>
-static int launch_act(const Args& a, hipStream_t s) {
+template <int NW, int NTH, int NTO, int NL, int ACT_H, int ACT_O, bool PAD = false>
+static int launch_act(const ArgsOf<PAD>& a, hipStream_t s) {
     constexpr int NTHR = NW * 64;
     constexpr int H = NTH * NW * 16;
     constexpr int HRS = H * 2 + 16;
@@ -688,7 +845,7 @@ static int launch_act(const Args& a, hipStream_t s) {
     const long long n_tiles = ceil_div(a.M, TE);
     const long long resident = (long long)g_cus * (lds_bytes <= 80 * 1024 && !g_opt_split3_one_wg ? 2 : 1);   // persistent workgroups
     const unsigned grid = (unsigned)(n_tiles < resident ? n_tiles : resident);
-    auto kern = k_mlp_f32_split3<NW, NTH, NTO, NL, ACT_H, ACT_O>;
+    auto kern = k_mlp_f32_split3<NW, NTH, NTO, NL, ACT_H, ACT_O, PAD>;
     HGNN_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     kern<<<grid, NTHR, lds_bytes, s>>>(a);
     HGNN_CHECK_HIP(hipGetLastError());
@@ -698,18 +855,20 @@ static int launch_act(const Args& a, hipStream_t s) {
 // activation codes as template parameters for the combinations the models use (hidden GELU + Tanh / GELU output:
 // edge / node / supernode / superedge networks and encoders; Tanh + Tanh: the hidden layers of the score heads);
 // anything else runs the runtime-switch instantiation
-template <int NW, int NTH, int NTO, int NL>
-static int launch(const Args& a, hipStream_t s) {
+template <int NW, int NTH, int NTO, int NL, bool PAD = false>
+static int launch(const ArgsOf<PAD>& a, hipStream_t s) {
     bool hidden_gelu = true, hidden_tanh = true;
     for (int l = 0; l + 1 < NL; ++l) {
         hidden_gelu = hidden_gelu && a.act[l] == HGNN_ACT_GELU;
         hidden_tanh = hidden_tanh && a.act[l] == HGNN_ACT_TANH;
     }
     const int out = a.act[NL - 1];
-    if (hidden_gelu && out == HGNN_ACT_TANH) return launch_act<NW, NTH, NTO, NL, HGNN_ACT_GELU, HGNN_ACT_TANH>(a, s);
-    if (hidden_gelu && out == HGNN_ACT_GELU) return launch_act<NW, NTH, NTO, NL, HGNN_ACT_GELU, HGNN_ACT_GELU>(a, s);
-    if (hidden_tanh && out == HGNN_ACT_TANH) return launch_act<NW, NTH, NTO, NL, HGNN_ACT_TANH, HGNN_ACT_TANH>(a, s);
-    return launch_act<NW, NTH, NTO, NL, -1, -1>(a, s);
+    if (hidden_gelu && out == HGNN_ACT_TANH) return launch_act<NW, NTH, NTO, NL, HGNN_ACT_GELU, HGNN_ACT_TANH, PAD>(a, s);
+    if (hidden_gelu && out == HGNN_ACT_GELU) return launch_act<NW, NTH, NTO, NL, HGNN_ACT_GELU, HGNN_ACT_GELU, PAD>(a, s);
+    if constexpr (!PAD) {   // (score heads: no PAD shape)
+        if (hidden_tanh && out == HGNN_ACT_TANH) return launch_act<NW, NTH, NTO, NL, HGNN_ACT_TANH, HGNN_ACT_TANH>(a, s);
+    }
+    return launch_act<NW, NTH, NTO, NL, -1, -1, PAD>(a, s);
 }
 
 }  // namespace f3
@@ -761,6 +920,60 @@ extern "C" int hgnn_mlp_forward_f32_split3(const hgnn_mlp_desc* d, float* out, h
     if (d->n_layers == 2 && o == 256 && f3::g_opt_split3_rows128 == 2 && d->M >= 65536) return f3::r64x2::launch_tile(a, stream);
     if (d->n_layers == 2) return o == 256 ? f3::launch<8, 4, 2, 2>(a, stream) : f3::launch<4, 4, 2, 2>(a, stream);
     return o == 256 ? f3::launch<8, 4, 2, 3>(a, stream) : f3::launch<4, 4, 2, 3>(a, stream);
+}
+
+// Widths between the grid's on the 64-row kernel's PAD instantiations: 16-column segments (no small-K mode), the
+// padded entry's storage fields, no dumps
+static const MlpDescRules kRulesF32Split3Padded = {/*seg_multiple*/ 16, /*padded_storage*/ true, /*layers*/ 2, 3,
+                                                   /*ln_everywhere*/ true, /*save_pre*/ false, /*max_pre*/ 2,
+                                                   /*m_int32*/ true};
+
+// the grid width P a hidden width h runs on: 128 (4 waves: H = 256, O = 128) or 256 (8 waves: H = 512, O = 256)
+static int split3_pad_grid(int h) { return (h % 16 != 0 || h <= 128 || h > 512) ? 0 : (h <= 256 ? 128 : 256); }
+
+extern "C" int hgnn_mlp_supported_f32_split3_padded(const hgnn_mlp_desc* d) {
+    if (!mlp_desc_shape_ok(d, kRulesF32Split3Padded) || d->w0_cols != 0) return 0;
+    for (int s = 0; s < d->n_seg; ++s)
+        if (d->seg_width[s] % 16 != 0) return 0;   // small-K mode stays with the exact kernel
+    const int n = d->n_layers;
+    const int h = d->width[1], o = d->width[n];
+    const int P = split3_pad_grid(h);
+    if (P == 0) return 0;
+    // K -> h (-> h) -> o: hidden layers stored 2P wide, the last layer as P rows
+    if (o < 4 || (o & 3) != 0 || 2 * o > h || d->w_last_rows != P) return 0;
+    return 1;
+}
+
+extern "C" int hgnn_mlp_forward_f32_split3_padded(const hgnn_mlp_desc* d, float* out, hgnn_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    HGNN_REQUIRE(d != nullptr && out != nullptr, "hgnn_mlp_forward_f32_split3_padded: NULL argument");
+    if (!hgnn_mlp_supported_f32_split3_padded(d)) {
+        set_error("hgnn_mlp_forward_f32_split3_padded: unsupported shape (see hgnn_mlp_supported_f32_split3_padded in "
+                  "include/hgnn_hip.h: K -> h (-> h) -> o with LayerNorm everywhere, h a multiple of 16 in (128, 512], "
+                  "o a multiple of 4 in [4, h / 2], every segment a multiple of 16 wide, no save_pre, parameters zero "
+                  "padded to the next grid width and split)");
+        return HGNN_ERR_UNSUPPORTED;
+    }
+    if (d->M == 0) return HGNN_OK;
+    static const char fn[] = "hgnn_mlp_forward_f32_split3_padded";
+    const int n = d->n_layers;
+    f3::ArgsPad a;
+    HGNN_TRY(unpack_segments(a, d, fn));
+    // the stored columns of W[0]: every kept segment's block padded to whole 128-column panels
+    a.K1 = 0;
+    for (int s = 0; s < d->n_seg; ++s) a.K1 += (d->seg_width[s] + f3::PK - 1) / f3::PK * f3::PK;
+    for (int s = d->n_seg; s < 3; ++s) a.seg_table[s] = a.seg_table[0];   // as hgnn_mlp_forward_f32_split3
+    for (int l = 0; l < 3; ++l) {
+        HGNN_TRY(unpack_layer(a, d, l, fn));
+        a.save_pre[l] = nullptr;
+        a.real[l] = l < n ? d->width[l + 1] : 0;
+    }
+    a.stagger = 0;
+    HGNN_TRY(unpack_pre(a, d, fn));
+    HGNN_TRY(unpack_out_skip(a, d, out, fn));
+    const bool wide = split3_pad_grid(d->width[1]) == 256;
+    if (n == 2) return wide ? f3::launch<8, 4, 2, 2, true>(a, stream) : f3::launch<4, 4, 2, 2, true>(a, stream);
+    return wide ? f3::launch<8, 4, 2, 3, true>(a, stream) : f3::launch<4, 4, 2, 3, true>(a, stream);
 }
 
 extern "C" int hgnn_linear_f32_split3(const float* x, int64_t M, int32_t K, const void* w_split, int32_t N,

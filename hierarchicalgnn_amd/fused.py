@@ -52,7 +52,7 @@ stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0, "library_c
 _ctx_options = contextvars.ContextVar("hgnn_fused_options", default=None)
 _ctx_training_forward = contextvars.ContextVar("hgnn_fused_training_forward", default=0)
 _OPTION_NAMES = ("enabled", "train_enabled", "preproject", "preproject_bf16", "fp32_split3", "fp32_split3_train",
-                 "bf16_split", "train_bf16_enabled", "strict")
+                 "bf16_split", "train_bf16_enabled", "strict", "split3_padded")
 
 
 def _opt(name: str):
@@ -65,7 +65,7 @@ def _opt(name: str):
 @contextlib.contextmanager
 def options(**overrides):
     """Context-local dispatch overrides: ``enabled``, ``train_enabled``, ``preproject``, ``preproject_bf16``,
-    ``fp32_split3``, ``fp32_split3_train``, ``bf16_split``, ``train_bf16_enabled``, ``strict``.
+    ``fp32_split3``, ``fp32_split3_train``, ``bf16_split``, ``train_bf16_enabled``, ``strict``, ``split3_padded``.
     ``strict``: ``concat_mlp`` raises instead of evaluating a Sequential on the library path (see ``set_strict``).
     Nested contexts stack; nothing outside the ``with`` block (or in another thread) sees the change.
     NOTE for training: autograd runs the backward (and the recompute of reentrant checkpoints) on its own worker
@@ -272,13 +272,28 @@ def _layout_bf16_split(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
     return 0, 0, lambda: (_prepared_weight(lin.weight, cols),) + raw[1:]
 
 
+def _layout_f32_split3_padded(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
+    """widths between the split-bf16 kernel's: the split stream of the weight zero padded to the instantiation of P_grid
+    (layout: hgnn_mlp_supported_f32_split3_padded in include/hgnn_hip.h), zero-padded vectors; cached copies.  ``cols``:
+    the column blocks of the kept segments (always given for the first layer: each is padded to whole panels)"""
+    if ln is None or small_k:
+        return None
+    last = l == n - 1
+    rows = P_grid if last else 2 * P_grid
+
+    def make():
+        W = _split3_padded_weight(lin.weight, rows, 2 * P_grid if l > 0 else None, cols)
+        return (W, _padded_param(lin.bias, rows), _padded_param(ln.weight, rows), _padded_param(ln.bias, rows))
+    return 0, rows if last else 0, make
+
+
 _LAYOUTS = {"f32": _layout_f32, "f32_padded": _layout_f32_padded, "f32_split3": _layout_f32_split3,
-            "bf16": _layout_bf16, "bf16_split": _layout_bf16_split}
+            "f32_split3_padded": _layout_f32_split3_padded, "bf16": _layout_bf16, "bf16_split": _layout_bf16_split}
 
 
 def _preprojections(tables, cols, proj, lin0, bf16: bool, split_proj: bool, width: int):
     """{i: tables[i] W_i^T  [rows, H]} for i in ``proj`` (W_i: columns ``cols[i]`` of the first Linear), zero padded to
-    ``width`` columns (f32_padded: the padded W[0] rows).  ``split_proj``: by ``_split3_project`` where it has the shape"""
+    ``width`` columns (f32_padded, f32_split3_padded: the padded W[0] rows).  ``split_proj``: by ``_split3_project`` where it has the shape"""
     P = {}
     if split_proj and proj:
         # both segments of one table (nodes[graph[0]], nodes[graph[1]]) in one launch
@@ -303,7 +318,7 @@ def _preprojections(tables, cols, proj, lin0, bf16: bool, split_proj: bool, widt
 
 def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = False, dry: bool = False, layers=None):
     """(descriptor, keep-alive list, M, n_out) for ``hgnn_mlp_forward_<entry>`` (``entry`` in f32, f32_padded,
-    f32_split3, bf16, bf16_split), or None.  ``layers``: ``_parse(net)`` when the caller has it (then ``net`` is not read).
+    f32_split3, f32_split3_padded, bf16, bf16_split), or None.  ``layers``: ``_parse(net)`` when the caller has it (then ``net`` is not read).
 
     One walk for every kernel: the segments (one row count M, int32 gather indices, pre-projected segments
     ``hgnn_mlp_desc.n_pre`` vs the ones kept in the kernel's K loop), the layers (chained widths, one LayerNorm eps)
@@ -327,8 +342,9 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
     if more or lin0.in_features != sum(ws) or not lin0.weight.is_cuda:
         return None
     hidden = int(lin0.out_features)
-    P_grid = _pad_grid(hidden) if entry == "f32_padded" else 0
-    if entry == "f32_padded" and (P_grid == 0 or len(layers) < 2):
+    padded = entry in ("f32_padded", "f32_split3_padded")
+    P_grid = _pad_grid(hidden) if padded else 0
+    if padded and (P_grid == 0 or len(layers) < 2):
         return None
     if bf16:
         pre = _opt("preproject_bf16")
@@ -356,7 +372,8 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
             n_kept += 1
     d.n_seg, d.n_pre = n_kept, n_pre
     # the kernel's K loop only sees the kept segments
-    kept_cols = tuple(c for i, c in enumerate(cols) if i not in proj) if proj else None
+    # (f32_split3_padded pads every kept segment's block to whole panels: it is told the blocks in any case)
+    kept_cols = tuple(c for i, c in enumerate(cols) if i not in proj) if proj or entry == "f32_split3_padded" else None
     n = d.n_layers = len(layers)
     o_l = K = d.width[0] = sum(ws) - sum(ws[i] for i in proj)
     small_k = not bf16 and any(w % 16 for w in ws)
@@ -568,6 +585,16 @@ def _split3(net, train: bool = False) -> bool:
     return _fp32_split3 if flag is None else bool(flag)
 
 
+def _split3_stream(W: torch.Tensor) -> torch.Tensor:
+    """fp32 W [F, K] (F % 16 == 0, K % 32 == 0) as its bf16 split stream in A-fragment order"""
+    hi = W.to(torch.bfloat16)
+    mid = (W - hi.float()).to(torch.bfloat16)
+    F, K = W.shape
+    # per 32-wide k-chunk: the chunk's W_hi columns, then its W_mid columns (virtual chunks 2c, 2c + 1)
+    Wv = torch.stack([hi.view(F, K // 32, 32), mid.view(F, K // 32, 32)], dim=2).reshape(F, 2 * K)
+    return _fragment_order(Wv.contiguous())
+
+
 def _split3_weight(weight, kept_cols, panels: bool, transpose: bool = False):
     """bf16 split stream of an fp32 Linear weight (per 32-wide k-chunk of the kept columns: W_hi, then W_mid) in
     A-fragment order, cached per weight object and version (``_cached``)"""
@@ -577,13 +604,37 @@ def _split3_weight(weight, kept_cols, panels: bool, transpose: bool = False):
             W = torch.cat([W[:, c0:c1] for c0, c1 in kept_cols], dim=1)
         if transpose:
             W = W.t().contiguous()
-        hi = W.to(torch.bfloat16)
-        mid = (W - hi.float()).to(torch.bfloat16)
-        F, K = W.shape
-        # per 32-wide k-chunk: the chunk's W_hi columns, then its W_mid columns (virtual chunks 2c, 2c + 1)
-        Wv = torch.stack([hi.view(F, K // 32, 32), mid.view(F, K // 32, 32)], dim=2).reshape(F, 2 * K)
-        return _fragment_order(Wv.contiguous())
+        return _split3_stream(W)
     return _cached(weight, ("split3", kept_cols, panels, transpose), make)
+
+
+def _split3_padded_weight(weight, rows: int, cols: Optional[int], kept_cols):
+    """``_split3_weight``'s stream of the zero-padded weight (hgnn_mlp_forward_f32_split3_padded): [out, in] -> ``rows``
+    rows; first layer (``kept_cols``): every kept column block padded to the next multiple of 128 columns; other layers:
+    ``cols`` columns.  Cached per weight object and version under its own key"""
+    def make():
+        W = weight.detach().float()
+        if kept_cols is not None:
+            W = torch.cat([torch.nn.functional.pad(W[:, c0:c1], (0, -(c1 - c0) % 128)) for c0, c1 in kept_cols], dim=1)
+        width = cols if cols is not None else int(W.shape[1])
+        out = torch.zeros((rows, width), dtype=W.dtype, device=W.device)
+        out[:W.shape[0], :W.shape[1]] = W
+        return _split3_stream(out)
+    return _cached(weight, ("split3_padded", rows, cols, kept_cols), make)
+
+
+_split3_padded = os.environ.get("HGNN_SPLIT3_PADDED", "0") == "1"
+
+
+def set_split3_padded(flag: bool) -> None:
+    """OPT-IN (HGNN_SPLIT3_PADDED=1, ``options(split3_padded=True)``): no-grad forwards of the fp32 cell networks at
+    widths BETWEEN the split-bf16 kernel's (hidden width in (128, 512], e.g. latent 96, 144, 160, 192) run the split-bf16
+    arithmetic on zero-padded parameters (hgnn_mlp_forward_f32_split3_padded) instead of the exact fp32 kernel on them
+    (hgnn_mlp_forward_f32_padded).  Only where the split-bf16 arithmetic applies at all (``_split3``): a module pinned
+    with ``hparams["fp32_gemm"] = "exact"``, a ``training_forward`` and every call autograd records keep the exact
+    kernel.  Default off."""
+    global _split3_padded
+    _split3_padded = bool(flag)
 
 
 def _split3_linear(x: torch.Tensor, weight, cols, net) -> Optional[torch.Tensor]:
@@ -656,11 +707,19 @@ def _is_bf16(segments) -> bool:
     return all(t.dtype == torch.bfloat16 for t, _ in segments)
 
 
+def _narrow_encoder(layers) -> bool:
+    """the supernode encoder's shape (``_layout_f32``'s rule): three layers whose last is up to 15 features narrower than
+    half the hidden width.  It stays on the exact kernels when ``split3_padded`` is on"""
+    h, o = layers[0][0].out_features, layers[-1][0].out_features
+    return len(layers) == 3 and h // 2 - 16 < o < h // 2
+
+
 class _Route(NamedTuple):
     """what ``_run`` launches for one call (``_route``)"""
     net: nn.Module
     layers: list               # _parse(net)
-    entry: str                 # each launch calls hgnn_mlp_forward_<entry>: f32, f32_split3, bf16, bf16_split or f32_padded
+    entry: str                 # each launch calls hgnn_mlp_forward_<entry>: f32, f32_split3, bf16, bf16_split, f32_padded
+                               # or f32_split3_padded
     split_proj: bool = False   # f32_split3: pre-projections in the kernel's arithmetic (``_descriptor``)
     chain: bool = False        # one launch per LayerNorm'ed layer (+ a trailing plain Linear)
     head: bool = False         # score head: the plain last Linear runs outside the kernel, on the hidden rows
@@ -769,7 +828,12 @@ def _route(net, segments, skip, *, train: bool, allow_chain: bool = True) -> Opt
     if not ok and not chain:
         # widths between the grid's (latent 48, 96, 160, 192, hidden_ratio 3, ...): zero-padded parameters on the next
         # grid instantiation of the exact fp32 kernel
-        return _Route(net, layers, "f32_padded") if dry("f32_padded")[1] else None
+        if not dry("f32_padded")[1]:
+            return None
+        if _opt("split3_padded") and _split3(net) and not _narrow_encoder(layers) and dry("f32_split3_padded")[1]:
+            # opt-in: the split-bf16 arithmetic on the same zero padding (cell networks with a hidden width above 128)
+            return _Route(net, layers, "f32_split3_padded")
+        return _Route(net, layers, "f32_padded")
     if _split3(net) and skip is None and len(layers) == 3 and plain_last \
             and layers[0][0].out_features in (256, 512) and layers[1][0].out_features == layers[0][0].out_features \
             and all(t.dtype == torch.float32 and int(t.shape[1]) % 128 == 0 for t, _ in segments):
@@ -812,6 +876,8 @@ def _forward(entry, d, out, dev):
         stats["split3_calls"] = stats.get("split3_calls", 0) + 1
     elif entry == "f32_padded":
         stats["padded_calls"] += 1
+    elif entry == "f32_split3_padded":
+        stats["split3_padded_calls"] = stats.get("split3_padded_calls", 0) + 1
 
 
 def _launch(layers, segments, skip, entry, split_proj=False, out=None):

@@ -454,6 +454,34 @@ int hgnn_mlp_forward_bf16_split(const hgnn_mlp_desc* d, void* out, hgnn_stream_t
 int hgnn_mlp_supported_f32_split3(const hgnn_mlp_desc* d);
 int hgnn_mlp_forward_f32_split3(const hgnn_mlp_desc* d, float* out, hgnn_stream_t stream);
 
+/* The SPLIT-bf16 arithmetic of hgnn_mlp_forward_f32_split3 at widths BETWEEN its two (latent 96, 144, 160, 192,
+ * hidden = 3 x latent, ...): its 64-row kernel on zero-padded, split parameters.  No-grad forward, opt-in in the Python
+ * layer (fused.set_split3_padded).
+ *   cell networks only: K -> h (-> h) -> o, 2 or 3 layers, LayerNorm on every layer, fp32 rows, h % 16 == 0,
+ *       128 < h <= 512, o % 4 == 0, 4 <= o <= h / 2; 1..3 segments, each a positive multiple of 16 wide (no small-K
+ *       mode); skip and n_pre <= 2 allowed; save_pre refused; M < 2^31.
+ * Let P = 128 when h <= 256, else 256 (the 4-wave / 8-wave instantiations: 2P hidden and P output features stored).
+ * width[] and seg_width[] carry the REAL widths; the storage the kernel reads follows from them, as for
+ * hgnn_mlp_forward_f32_padded:
+ *   W[0]            [2P, Kp] rows h .. 2P-1 zero; Kp: each kept segment's column block zero padded to the next multiple
+ *                   of 128 columns (a segment w wide is ceil(w / 128) input panels);
+ *   W[1] (3 layers) [2P, 2P] rows and columns h .. 2P-1 zero;
+ *   last W          [P, 2P]  rows o .. P-1 and columns h .. 2P-1 zero;
+ *   each padded W is then stored as its split stream (hi / mid chunks in A-fragment order), exactly as
+ *       hgnn_mlp_forward_f32_split3 reads an unpadded one;
+ *   b, ln_w, ln_b of every layer: as many fp32 entries as the layer's W has rows, the padded ones ZERO (ln_w too: a
+ *       padded feature must come out as 0, it is the next layer's input);
+ *   w_last_rows = P, checked (w0_cols = 0);
+ *   pre_table[s]    fp32 [rows, 2P] = table W_s^T, columns h .. 2P-1 zero.
+ * Rows in HBM keep their real widths and strides: segment tables [rows, seg_width[s]] (a 16-byte piece past a
+ * segment's width is never read), skip and out [M, o].  LayerNorm statistics run over the real features only: every
+ * wave centres its own real features, the waves' (mean, M2) pairs are pooled with their real counts, which may be 0.
+ * The check accepts the grid shapes K -> 2L (-> 2L) -> L, L in {128, 256}, too (segments then multiples of 16 rather
+ * than 128); on a descriptor both entries accept -- up to w_last_rows -- this one returns the bits of
+ * hgnn_mlp_forward_f32_split3's 64-row kernel. */
+int hgnn_mlp_supported_f32_split3_padded(const hgnn_mlp_desc* d);
+int hgnn_mlp_forward_f32_split3_padded(const hgnn_mlp_desc* d, float* out, hgnn_stream_t stream);
+
 /* out[M, N] = x[M, K] . W^T (+ skip), all fp32 in HBM, the product as split-bf16 (same arithmetic and the same
  * weight stream layout as hgnn_mlp_forward_f32_split3: w_split = the split stream of W [N, K]): the M-row data-gradient
  * GEMMs of the fp32 training backward.  K a multiple of 128, N in {256, 512}; skip [M, N] or NULL. */

@@ -10,6 +10,11 @@ nodes, and the EC-IN 14-cell forward at latent 96, against
 Public API only (``mlp.concat_mlp``, the model mirrors), so the same file runs on a commit without the padded kernels,
 where the "fused" variant of a non-grid width is the library path too (``padded_calls`` says which one ran).
 
+``--split3``: the opt-in split-bf16 route at these widths (``fused.options(split3_padded=True)``,
+hgnn_mlp_forward_f32_split3_padded) against the route with the option off in the same session (the exact padded kernel)
+and the native neighbour's split-bf16 default (latent 256: also its 64-row kernel, which is what the padded entry
+launches, next to the 128-row tile); the same three rows.
+
 Method: device events around ``--inner`` back-to-back calls, every variant warmed up first, the variants ALTERNATED
 inside each of ``--repeats`` (>= 7) rounds; per variant the median per-call time and the spread (min, max) over the
 rounds.  One JSON document on stdout (``--out FILE`` also writes it).
@@ -22,7 +27,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from hierarchicalgnn_amd import fused, make_mlp, mlp, synth  # noqa: E402
+from hierarchicalgnn_amd import _lib, fused, make_mlp, mlp, synth  # noqa: E402
 
 
 def _time(fn, inner):
@@ -112,6 +117,75 @@ def ec_in(L, x, ei, repeats):
                 fused_vs_library_max_rel=err, **res)
 
 
+def _split3_padded(fn):
+    def run():
+        with fused.options(split3_padded=True):
+            return fn()
+    return run
+
+
+def _rows64(fn):
+    """the neighbour's split-bf16 default on its 64-row kernel (the padded entry never launches the 128-row tile)"""
+    def run():
+        lib = _lib.load()
+        _lib.check(lib.hgnn_set_option(b"mlp_split3_rows128", 0))
+        try:
+            return fn()
+        finally:
+            _lib.check(lib.hgnn_set_option(b"mlp_split3_rows128", 1))
+    return run
+
+
+def edge_update_split3(L, neighbour, graph, N, repeats, inner):
+    M = int(graph.shape[1])
+
+    def make(width):
+        torch.manual_seed(width)
+        net = make_mlp(3 * width, 2 * width, width, 2, layer_norm=True, output_activation="Tanh",
+                       hidden_activation="GELU").cuda()
+        nodes = torch.randn(N, width, device="cuda")
+        edges = torch.randn(M, width, device="cuda")
+        segs = [(nodes, graph[0]), (nodes, graph[1]), (edges, None)]
+        return lambda: mlp.concat_mlp(net, segs, skip=edges)
+
+    own, nb = make(L), make(neighbour)
+    on = _split3_padded(own)
+    with torch.no_grad():
+        n0, p0 = fused.stats.get("split3_padded_calls", 0), fused.stats.get("padded_calls", 0)
+        a = on()
+        ran = fused.stats.get("split3_padded_calls", 0) == n0 + 1 and fused.stats.get("padded_calls", 0) == p0
+        b = own()
+        ran = ran and fused.stats.get("padded_calls", 0) == p0 + 1
+        err = float((a - b).abs().max() / b.abs().max())
+        del a, b
+        variants = {f"latent{L}_exact_padded": own, f"latent{L}_split3_padded": on, f"latent{neighbour}_default": nb}
+        if neighbour == 256:
+            variants[f"latent{neighbour}_default_rows64"] = _rows64(nb)
+        res = _alternate(variants, repeats, inner)
+    return dict(shape=f"edge update 3x{L} -> {2 * L} -> {L}, M = {M}, N = {N}", split3_padded_kernel_ran=ran,
+                split3_vs_exact_max_rel=err, **res)
+
+
+def ec_in_split3(L, x, ei, repeats):
+    from hierarchicalgnn_amd.models import EC_InteractionGNN
+    torch.manual_seed(0)
+    hp = dict(spatial_channels=3, latent=L, hidden=2 * L, n_interaction_graph_iters=14, nb_node_layer=3, nb_edge_layer=2,
+              output_layers=3, hidden_output_activation="GELU", hidden_activation="GELU", layernorm=True,
+              share_weight=False)
+    model = EC_InteractionGNN(hp).cuda().eval()
+    run = lambda: model(x, ei)   # noqa: E731
+    on = _split3_padded(run)
+    with torch.no_grad():
+        n0 = fused.stats.get("split3_padded_calls", 0)
+        a = on()
+        calls = fused.stats.get("split3_padded_calls", 0) - n0
+        b = run()
+        diff = float((a - b).abs().max())
+        res = _alternate({"exact_padded": run, "split3_padded": on}, repeats, 1)
+    return dict(shape=f"EC-IN forward, 14 cells, latent {L}, E = {int(ei.shape[1])}", split3_padded_calls_per_forward=calls,
+                split3_vs_exact_max_abs_score=diff, **res)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--repeats", type=int, default=9)
@@ -119,6 +193,9 @@ def main():
     ap.add_argument("--nodes", type=int, default=120_000)
     ap.add_argument("--edges", type=int, default=1_000_000, help="undirected edges (the update runs on twice as many)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--split3", action="store_true",
+                    help="measure the opt-in split-bf16 route at these widths against the exact padded one "
+                         "(default --out: profiles/mlp_widths_split3_bench.json)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_mlp_widths: needs a GPU (there is no CPU path to time)")
@@ -127,11 +204,21 @@ def main():
     x, ei = synth.trackml_event(args.nodes, args.edges, seed=1)
     x, ei = x.cuda(), ei.cuda()
     graph = synth.directed(ei).cuda()
-    doc = dict(device=torch.cuda.get_device_name(0), repeats=args.repeats, inner=args.inner,
-               method="device events, variants alternated inside each repeat, median (min, max) per call",
-               edge_update=[edge_update(96, 128, graph, args.nodes, args.repeats, args.inner),
-                            edge_update(192, 256, graph, args.nodes, args.repeats, args.inner)],
-               ec_in=ec_in(96, x, ei, args.repeats))
+    head = dict(device=torch.cuda.get_device_name(0), repeats=args.repeats, inner=args.inner,
+                method="device events, variants alternated inside each repeat, median (min, max) per call")
+    if args.split3:
+        if args.out is None:
+            args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                    "mlp_widths_split3_bench.json")
+        doc = dict(**head,
+                   edge_update=[edge_update_split3(96, 128, graph, args.nodes, args.repeats, args.inner),
+                                edge_update_split3(192, 256, graph, args.nodes, args.repeats, args.inner)],
+                   ec_in=ec_in_split3(96, x, ei, args.repeats))
+    else:
+        doc = dict(**head,
+                   edge_update=[edge_update(96, 128, graph, args.nodes, args.repeats, args.inner),
+                                edge_update(192, 256, graph, args.nodes, args.repeats, args.inner)],
+                   ec_in=ec_in(96, x, ei, args.repeats))
     txt = json.dumps(doc, indent=1)
     print(txt)
     if args.out:
