@@ -164,6 +164,15 @@ _SIGNATURES = {
     "hgnn_wgrad_f32_workspace_bytes": (c_int, [c_int64, c_int32, c_int32, POINTER(c_size_t)]),
     "hgnn_wgrad_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64,
                                c_void_p, c_size_t, c_void_p]),
+    "hgnn_project_f32": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                 c_void_p, c_int64, c_void_p]),
+    "hgnn_linear_narrow_f32": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32,
+                                       c_void_p, c_int64, c_void_p]),
+    "hgnn_outer_narrow_f32": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p,
+                                      c_void_p, c_int64, c_void_p]),
+    "hgnn_wgrad_narrow_f32_workspace_bytes": (c_int, [c_int64, c_int32, c_int32, POINTER(c_size_t)]),
+    "hgnn_wgrad_narrow_f32": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int64,
+                                      c_void_p, c_void_p, c_size_t, c_void_p]),
     "hgnn_mlp_backward_layer_supported_bf16": (c_int, [c_int32, c_int32]),
     "hgnn_mlp_backward_layer_bf16": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

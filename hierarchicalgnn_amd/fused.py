@@ -41,7 +41,11 @@ _train_enabled = True
 # gradient of the bf16 training backward went through a library GEMM; bwd_layer_calls: launches of the fused backward
 # layer; hybrid_train_calls: encoders under autograd on the fp32 first layer + bf16 tail (mlp.concat_mlp);
 # bwd_layer_f32_calls: launches of the exact-fp32 fused backward layer (set_bwd_layer_f32).  Created on first use:
-# split3_wgrad_calls / wgrad_f32_calls / library_wgrad_calls, the branch ``_atb`` took for a weight gradient
+# split3_wgrad_calls / wgrad_f32_calls / narrow_wgrad_calls / library_wgrad_calls, the branch ``_atb`` took for a weight
+# gradient; project_f32_calls / library_project_calls, the branch of a forward pre-projection; narrow_linear_calls /
+# narrow_outer_calls / library_head_calls, a head's plain last Linear (``set_project_f32``, ``set_narrow_f32``).  While
+# ``set_narrow_f32`` is on, library_dgrad_calls also counts a first-layer input gradient of the fp32 backward that stays
+# on the library
 stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0, "library_calls": 0, "library_dgrad_calls": 0,
          "bwd_layer_calls": 0, "hybrid_train_calls": 0, "bwd_layer_f32_calls": 0}
 
@@ -293,7 +297,8 @@ _LAYOUTS = {"f32": _layout_f32, "f32_padded": _layout_f32_padded, "f32_split3": 
 
 def _preprojections(tables, cols, proj, lin0, bf16: bool, split_proj: bool, width: int):
     """{i: tables[i] W_i^T  [rows, H]} for i in ``proj`` (W_i: columns ``cols[i]`` of the first Linear), zero padded to
-    ``width`` columns (f32_padded, f32_split3_padded: the padded W[0] rows).  ``split_proj``: by ``_split3_project`` where it has the shape"""
+    ``width`` columns (f32_padded, f32_split3_padded: the padded W[0] rows).  ``split_proj``: by ``_split3_project`` where it has the shape;
+    with ``set_project_f32`` fp32 tables go to ``_exact_project`` (hgnn_project_f32); what is left is ``torch.matmul``"""
     P = {}
     if split_proj and proj:
         # both segments of one table (nodes[graph[0]], nodes[graph[1]]) in one launch
@@ -303,9 +308,20 @@ def _preprojections(tables, cols, proj, lin0, bf16: bool, split_proj: bool, widt
             res = _split3_project(tables[grp[0]].detach(), lin0.weight, [cols[i] for i in grp])
             if res is not None:
                 P.update(zip(grp, res))
+    if _project_f32_on and not bf16:
+        # set_project_f32: the exact route's projections on hgnn_project_f32 (fp32 MFMA, k-ordered chains), both
+        # segments of one table in one launch; the split-bf16 projection above keeps precedence
+        rest = [i for i in proj if i not in P]
+        same = len(rest) == 2 and tables[rest[1]].data_ptr() == tables[rest[0]].data_ptr() \
+            and tables[rest[1]].shape == tables[rest[0]].shape
+        for grp in ([rest] if same else [[i] for i in rest]):
+            res = _exact_project(tables[grp[0]].detach(), lin0.weight, [cols[i] for i in grp], width)
+            if res is not None:
+                P.update(zip(grp, res))
     for i in proj:
         if i in P:
             continue
+        stats["library_project_calls"] = stats.get("library_project_calls", 0) + 1
         W_s = lin0.weight.detach()[:, cols[i][0]:cols[i][1]]
         with torch.autocast("cuda", enabled=False):
             # the kernel reads P in its row dtype; bf16: bf16 operands, fp32 accumulation, one rounding -- the
@@ -680,6 +696,21 @@ def _split3_project(table: torch.Tensor, weight, cols_list):
     return outs
 
 
+def _exact_project(table: torch.Tensor, weight, cols_list, width: int):
+    """``_split3_project``'s job in EXACT fp32 (ops.project_f32 / hgnn_project_f32): [table . W[:, cols]^T for cols in
+    cols_list] from one launch, the column blocks of ``weight`` read in place, zero padded to ``width`` columns; None
+    when the entry does not take the shape (K a multiple of 16 up to 512, N a multiple of 16 up to 1024)"""
+    K, N = int(table.shape[1]), int(weight.shape[0])
+    if table.dtype != torch.float32 or weight.dtype != torch.float32 or not table.is_cuda or not weight.is_cuda \
+            or K % 16 or not 16 <= K <= 512 or N % 16 or not 16 <= N <= 1024 or not 1 <= len(cols_list) <= 2:
+        return None
+    from .ops import project_f32
+    Wd = weight.detach()
+    res = project_f32(table, *[Wd[:, c0:c1] for c0, c1 in cols_list], width=width if width and N < width else None)
+    stats["project_f32_calls"] = stats.get("project_f32_calls", 0) + 1
+    return list(res)
+
+
 _bf16_split = True
 
 
@@ -913,18 +944,26 @@ def _run(r: _Route, segments, skip, out=None):
             # an [M, H] x [H, w<=32] product -- applied to the returned hidden rows
             hidden = _FusedMLPTrain.apply(r, indices, False, *tables, *params)
             stats["fused_head_train_calls"] = stats.get("fused_head_train_calls", 0) + 1
+            y = _head_linear(hidden, layers[2][0], True)
+            if y is not None:
+                return y
             return torch.nn.functional.linear(hidden, layers[2][0].weight, layers[2][0].bias)
         fn = _FusedMLPTrainBf16 if r.entry == "bf16_split" else _FusedMLPTrain
         return fn.apply(r, indices, skip is not None, *tables, *([skip] if skip is not None else []), *params)
     if r.head:
-        y = _launch(layers[:2], segments, None, r.entry, r.split_proj)
-        y = torch.nn.functional.linear(y, layers[2][0].weight, layers[2][0].bias)
+        hidden = _launch(layers[:2], segments, None, r.entry, r.split_proj)
+        y = _head_linear(hidden, layers[2][0], False)
+        if y is None:
+            y = torch.nn.functional.linear(hidden, layers[2][0].weight, layers[2][0].bias)
     elif r.chain:
         # one launch per layer; the hidden rows make one trip through HBM (fp32 at latent 512)
         y = None
         for i, layer in enumerate(layers):
             if layer[1] is None:                          # the plain last Linear of a head
-                y = torch.nn.functional.linear(y, layer[0].weight.to(y.dtype), layer[0].bias.to(y.dtype))
+                hidden, y = y, _head_linear(y, layer[0], False)
+                if y is None:
+                    y = torch.nn.functional.linear(hidden, layer[0].weight.to(hidden.dtype),
+                                                   layer[0].bias.to(hidden.dtype))
             else:
                 y = _launch([layer], segments, skip if i == len(layers) - 1 else None, r.entry)
                 segments = [(y, None)]
@@ -979,7 +1018,9 @@ def _atb(A: torch.Tensor, B: torch.Tensor, net=None) -> torch.Tensor:
     (``net`` given) and fp32 operands of at least 4096 rows: the hand-written split-K kernel on the bf16 matrix pipe
     (ops.wgrad_f32_split3: ~1.7 ms where the library paths below need 3.6-4 ms at n = 2M).  With ``set_wgrad_f32`` and
     fp32 device operands whose widths are multiples of 8 up to 1024: the exact fp32-MFMA split-K kernel (ops.wgrad_f32:
-    fixed order, the same bits on every device; 4.05 against 3.59 ms at n = 2M, profiles/wgrad_f32.json).  Otherwise
+    fixed order, the same bits on every device; 4.05 against 3.59 ms at n = 2M, profiles/wgrad_f32.json).  With
+    ``set_narrow_f32`` and one width <= 32 (the other a multiple of 4 up to 1024) that the kernel above does not take:
+    ops.wgrad_narrow_f32 (profiles/exact_tail.json).  Otherwise
     (``stats["library_wgrad_calls"]``): the library picks
     a small output tile without split-K for these (p*q/1024 workgroups walking all n rows: 1.2 ms for the
     8 GFLOP of n = 120k, ~110 TFLOP/s at n = 2M); a batched product over row blocks plus one sum fills the
@@ -997,6 +1038,15 @@ def _atb(A: torch.Tensor, B: torch.Tensor, net=None) -> torch.Tensor:
         from .ops import wgrad_f32
         stats["wgrad_f32_calls"] = stats.get("wgrad_f32_calls", 0) + 1
         return wgrad_f32(A, B)
+    # set_narrow_f32: one width <= 32 (the encoders' 3- and 6-wide tables) on hgnn_wgrad_narrow_f32, the other a multiple
+    # of 4 up to 1024; the narrow side goes first, so a [q <= 32] B gives the transposed result
+    if _narrow_f32_on and A.dtype == torch.float32 and B.dtype == torch.float32 and A.is_cuda and B.is_cuda \
+            and not (net is not None and _split3(net, train=True)):
+        p, q = int(A.shape[1]), int(B.shape[1])
+        if _narrow_widths(p, q) or _narrow_widths(q, p):
+            from .ops import wgrad_narrow_f32
+            stats["narrow_wgrad_calls"] = stats.get("narrow_wgrad_calls", 0) + 1
+            return wgrad_narrow_f32(A, B) if _narrow_widths(p, q) else wgrad_narrow_f32(B, A).t().contiguous()
     stats["library_wgrad_calls"] = stats.get("library_wgrad_calls", 0) + 1
     chunks = max(16, min(256, n // 8192))   # 4096 / 8192 rows per block measured equal, 32768 6 % slower
     c = n // chunks
@@ -1184,6 +1234,7 @@ class _FusedMLPTrain(torch.autograd.Function):
                 # Only a direct segment (the edge rows themselves) keeps M-row GEMMs.
                 dW_cols = []
                 col = 0
+                split3_train = _split3(ctx.net, train=True)   # keeps precedence over set_narrow_f32
                 for s_i in range(n_seg):
                     idx = indices[s_i]
                     tab = tables[s_i].contiguous()
@@ -1197,7 +1248,8 @@ class _FusedMLPTrain(torch.autograd.Function):
                                 grads_tables[s_i] = _bwd_layer_f32(S, W_s, None, None, None, 0, ctx.eps, weight=lw[0],
                                                                    cols=(col, col + w_s))[0]
                             else:
-                                grads_tables[s_i] = S @ W_s
+                                gt = None if split3_train else _narrow_dgrad(S, W_s, lw[0], (col, col + w_s))
+                                grads_tables[s_i] = gt if gt is not None else S @ W_s
                         del S
                     else:
                         dW_cols.append(_atb(dz, tab, ctx.net))
@@ -1212,6 +1264,8 @@ class _FusedMLPTrain(torch.autograd.Function):
                                 folded_skip = folded_skip or fold
                             else:
                                 gt = _split3_linear(dz, lw[0], (col, col + w_s), ctx.net)
+                                if gt is None and not split3_train:
+                                    gt = _narrow_dgrad(dz, W_s, lw[0], (col, col + w_s))
                                 grads_tables[s_i] = gt if gt is not None else dz @ W_s
                     col += w_s
                 grads_params[0] = dW_cols[0] if n_seg == 1 else torch.cat(dW_cols, dim=1)
@@ -1317,6 +1371,97 @@ def set_wgrad_f32(flag: bool) -> None:
     split-bf16 route keeps precedence; independent of ``set_bwd_layer_f32``."""
     global _wgrad_f32_on
     _wgrad_f32_on = bool(flag)
+
+
+# the forward pre-projections of the EXACT fp32 route on hgnn_project_f32 (csrc/project_f32.hip) instead of torch.matmul,
+# and its products with one side at most 32 wide on the narrow kernels (csrc/narrow_f32.hip).  OFF: the defaults are
+# decided by tools/bench_exact_tail.py and the 3 x spread rule (DESIGN.md section 3)
+_project_f32_on = os.environ.get("HGNN_PROJECT_F32", "0") == "1"
+_narrow_f32_on = os.environ.get("HGNN_NARROW_F32", "0") == "1"
+
+
+def set_project_f32(flag: bool) -> None:
+    """process default (the recompute of a checkpoint segment runs on autograd's thread, which no ``options`` context
+    reaches): ``_preprojections`` takes ``hgnn_project_f32`` for fp32 tables whose (K, N) the entry accepts -- the
+    no-grad exact route, both passes of a training step and the padded route (HGNN_PROJECT_F32=1).  bf16 rows and other
+    shapes keep ``torch.matmul``; the split-bf16 projection keeps precedence; independent of the other switches."""
+    global _project_f32_on
+    _project_f32_on = bool(flag)
+
+
+def set_narrow_f32(flag: bool) -> None:
+    """process default: the exact fp32 route's narrow products leave the library (HGNN_NARROW_F32=1) -- the plain last
+    Linear of a score head (forward ``hgnn_linear_narrow_f32``; backward ``hgnn_outer_narrow_f32`` +
+    ``hgnn_wgrad_narrow_f32`` with its column sums), the weight gradients ``_atb`` with one width <= 32 that
+    ``hgnn_wgrad_f32`` does not take, and the first layer's input gradients ``S @ W_s`` / ``dz @ W_s`` with w_s <= 32.
+    The split-bf16 training route keeps precedence; independent of the other switches."""
+    global _narrow_f32_on
+    _narrow_f32_on = bool(flag)
+
+
+def _narrow_widths(n: int, K: int) -> bool:
+    """the narrow kernels' shapes: n the narrow width, K the wide one"""
+    return 1 <= n <= 32 and 4 <= K <= 1024 and K % 4 == 0
+
+
+def _count(name: str) -> None:
+    stats[name] = stats.get(name, 0) + 1
+
+
+class _NarrowLinear(torch.autograd.Function):
+    """a head's plain last Linear ``hidden @ W^T + b`` with W [w <= 32, H] on the narrow kernels"""
+
+    @staticmethod
+    def forward(ctx, hidden, W, b):
+        from .ops import linear_narrow_f32
+        ctx.save_for_backward(hidden, W)
+        ctx.has_bias = b is not None
+        _count("narrow_linear_calls")
+        return linear_narrow_f32(hidden.detach(), W.detach(), b.detach() if b is not None else None)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .ops import outer_narrow_f32, wgrad_narrow_f32
+        hidden, W = ctx.saved_tensors
+        dy = dy.float()
+        dh = None
+        if ctx.needs_input_grad[0]:
+            _count("narrow_outer_calls")
+            dh = outer_narrow_f32(dy, W.detach())
+        db = torch.empty(int(W.shape[0]), dtype=torch.float32, device=dy.device) if ctx.has_bias else None
+        _count("narrow_wgrad_calls")
+        dW = wgrad_narrow_f32(dy, hidden, colsum=db)
+        return dh, dW, db
+
+
+def _head_linear(hidden, lin, differentiable: bool):
+    """the plain last Linear of a score head on the narrow kernels (``set_narrow_f32``), or None: the caller evaluates
+    its library expression, counted here"""
+    W, b = lin.weight, lin.bias
+    if _narrow_f32_on and hidden.is_cuda and hidden.dtype == torch.float32 and W.dtype == torch.float32 \
+            and (b is None or b.dtype == torch.float32) and _narrow_widths(int(W.shape[0]), int(W.shape[1])):
+        if differentiable:
+            return _NarrowLinear.apply(hidden, W, b)
+        from .ops import linear_narrow_f32
+        _count("narrow_linear_calls")
+        return linear_narrow_f32(hidden, W.detach(), b.detach() if b is not None else None)
+    _count("library_head_calls")
+    return None
+
+
+def _narrow_dgrad(x, W_s, weight, cols):
+    """``x @ W_s`` for the first layer's W_s = weight[:, cols] [H, w_s <= 32] on ``hgnn_linear_narrow_f32`` (its weight
+    is the small transposed copy W_s^T, cached per weight like ``_transposed_weight_f32``), or None: the caller's
+    library expression, counted here while ``set_narrow_f32`` is on"""
+    if not _narrow_f32_on:
+        return None
+    if x.is_cuda and x.dtype == torch.float32 and W_s.dtype == torch.float32 \
+            and _narrow_widths(int(W_s.shape[1]), int(W_s.shape[0])):
+        from .ops import linear_narrow_f32
+        _count("narrow_linear_calls")
+        return linear_narrow_f32(x, _transposed_weight_f32(W_s, weight, cols))
+    stats["library_dgrad_calls"] += 1
+    return None
 
 
 def _bwd_layer_f32_supported(K: int, N: int) -> bool:

@@ -713,3 +713,121 @@ def wgrad_f32(dz: torch.Tensor, rows: torch.Tensor, out: Optional[torch.Tensor] 
                                       ctypes.c_void_p(out.data_ptr()), int(out.stride(0)),
                                       _lib.ptr(ws), ws.numel(), _lib.current_stream(dz.device)), "hgnn_wgrad_f32")
     return out
+
+
+# ------------------------------------------------------------------ the exact route's projection and narrow products
+def _narrow_operand(t: torch.Tensor) -> torch.Tensor:
+    """a narrow-side operand ([M, n] rows, [n, K] weights) as the narrow kernels can read it: unit column stride and a
+    row stride that covers the width (4-byte alignment is all they need, so tab[N, 3] is read in place)"""
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
+
+
+def _ld(t: torch.Tensor) -> int:
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def project_f32(x: torch.Tensor, w0: torch.Tensor, w1: Optional[torch.Tensor] = None, width: Optional[int] = None):
+    """``x @ w0.T`` (and ``x @ w1.T``) for FP32 ``x[M, K]`` and ``w_b[N, K]`` in EXACT fp32 (``hgnn_project_f32``: every
+    product formed once on the fp32 MFMA, each output element a fmaf chain over k ascending, no split-K): the forward
+    pre-projection of the exact route, both segments of an edge update from one launch.  ``w0`` / ``w1`` may be column
+    blocks of one first Linear, read in place; views the kernel cannot read are copied (:func:`_wgrad_operand`).
+    ``width`` > N returns zero-filled ``[M, width]`` tensors with the product in the first N columns (the padded
+    route).  Returns a tuple with one tensor per weight block."""
+    _require_hip(x, "x")
+    ws = [w0] if w1 is None else [w0, w1]
+    for w in ws:
+        _require_hip(w, "w")
+    if x.dim() != 2 or any(w.dim() != 2 or w.shape[1] != x.shape[1] or w.shape != w0.shape for w in ws):
+        raise RuntimeError("project_f32: fp32 x[M, K] and w[N, K] blocks of one shape expected")
+    x = _wgrad_operand(x)
+    ws = [_wgrad_operand(w) for w in ws]
+    M, K, N = int(x.shape[0]), int(x.shape[1]), int(w0.shape[0])
+    if len(ws) == 2 and N > 1 and ws[0].stride(0) != ws[1].stride(0):
+        ws = [w.contiguous() for w in ws]
+        ws = [w if w.data_ptr() % 16 == 0 else w.clone() for w in ws]
+    cols = N if width is None else int(width)
+    if cols < N:
+        raise RuntimeError("project_f32: width must be at least N")
+    make = torch.empty if cols == N else torch.zeros
+    outs = [make((M, cols), dtype=torch.float32, device=x.device) for _ in ws]
+    if M == 0:   # nothing to launch (and an empty tensor has no address to hand over)
+        return tuple(outs)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().hgnn_project_f32(
+            _lib.ptr(x), _ld(x), M, K, _lib.ptr(ws[0]), _lib.ptr(ws[1]) if len(ws) > 1 else None, _ld(ws[0]), N,
+            _lib.ptr(outs[0]), _lib.ptr(outs[1]) if len(outs) > 1 else None, cols,
+            _lib.current_stream(x.device)), "hgnn_project_f32")
+    return tuple(outs)
+
+
+def linear_narrow_f32(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``x @ W.T + bias`` for FP32 ``x[M, K]`` and a NARROW ``W[n, K]``, n <= 32 (``hgnn_linear_narrow_f32``: fixed
+    order, a function of K alone; the bias joins last): a head's last Linear, the encoders' input gradient."""
+    _require_hip(x, "x")
+    _require_hip(W, "W")
+    if x.dim() != 2 or W.dim() != 2 or W.shape[1] != x.shape[1]:
+        raise RuntimeError("linear_narrow_f32: fp32 x[M, K] and W[n, K] expected")
+    x, W = _wgrad_operand(x), _narrow_operand(W)
+    M, K, n = int(x.shape[0]), int(x.shape[1]), int(W.shape[0])
+    if bias is not None:
+        _require_hip(bias, "bias")
+        if bias.numel() != n or not bias.is_contiguous():
+            raise RuntimeError("linear_narrow_f32: bias must be a contiguous fp32 [n] tensor")
+    out = torch.empty((M, n), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().hgnn_linear_narrow_f32(
+            _lib.ptr(x), _ld(x), M, K, _lib.ptr(W), _ld(W), _lib.ptr(bias) if bias is not None else None, n,
+            _lib.ptr(out), n, _lib.current_stream(x.device)), "hgnn_linear_narrow_f32")
+    return out
+
+
+def outer_narrow_f32(y: torch.Tensor, W: torch.Tensor, add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y @ W (+ add)`` for a NARROW FP32 ``y[M, n]``, n <= 32, and ``W[n, K]`` (``hgnn_outer_narrow_f32``: a fmaf
+    chain over j ascending, ``add`` joins last): a head's data gradient ``dy @ W``."""
+    _require_hip(y, "y")
+    _require_hip(W, "W")
+    if y.dim() != 2 or W.dim() != 2 or W.shape[0] != y.shape[1]:
+        raise RuntimeError("outer_narrow_f32: fp32 y[M, n] and W[n, K] expected")
+    y, W = _narrow_operand(y), _narrow_operand(W)
+    M, n, K = int(y.shape[0]), int(y.shape[1]), int(W.shape[1])
+    if add is not None:
+        _require_hip(add, "add")
+        if tuple(add.shape) != (M, K):
+            raise RuntimeError("outer_narrow_f32: add must be fp32 [M, K]")
+        add = add.contiguous()   # it shares out's row stride
+    out = torch.empty((M, K), dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.load().hgnn_outer_narrow_f32(
+            _lib.ptr(y), _ld(y), M, n, _lib.ptr(W), _ld(W), K, _lib.ptr(add) if add is not None else None,
+            _lib.ptr(out), K, _lib.current_stream(y.device)), "hgnn_outer_narrow_f32")
+    return out
+
+
+def wgrad_narrow_f32(y: torch.Tensor, x: torch.Tensor, colsum: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y^T @ x`` for a NARROW FP32 ``y[M, n]``, n <= 32, and ``x[M, K]`` (``hgnn_wgrad_narrow_f32``: split over the
+    rows in a fixed order, no atomics); ``colsum`` (fp32 [n]) receives the column sums of ``y``.  A head's weight and
+    bias gradient (``y = dy``, ``x = hidden``), the encoders' ``dW[:, cols]^T`` (``y = tab[N, 3]``, read in place)."""
+    _require_hip(y, "y")
+    _require_hip(x, "x")
+    if y.dim() != 2 or x.dim() != 2 or y.shape[0] != x.shape[0]:
+        raise RuntimeError("wgrad_narrow_f32: fp32 y[M, n] and x[M, K] expected")
+    y, x = _narrow_operand(y), _wgrad_operand(x)
+    M, n, K = int(y.shape[0]), int(y.shape[1]), int(x.shape[1])
+    if colsum is not None:
+        _require_hip(colsum, "colsum")
+        if colsum.numel() != n or not colsum.is_contiguous():
+            raise RuntimeError("wgrad_narrow_f32: colsum must be a contiguous fp32 [n] tensor")
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(lib.hgnn_wgrad_narrow_f32_workspace_bytes(M, n, K, ctypes.byref(nbytes)),
+               "hgnn_wgrad_narrow_f32_workspace_bytes")
+    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=y.device)
+    out = torch.empty((n, K), dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        _lib.check(lib.hgnn_wgrad_narrow_f32(
+            _lib.ptr(y), _ld(y), n, _lib.ptr(x), _ld(x), K, M, _lib.ptr(out), K,
+            _lib.ptr(colsum) if colsum is not None else None, _lib.ptr(ws), ws.numel(),
+            _lib.current_stream(y.device)), "hgnn_wgrad_narrow_f32")
+    return out

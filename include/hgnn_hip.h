@@ -560,6 +560,52 @@ int hgnn_wgrad_f32_workspace_bytes(int64_t M, int32_t Ho, int32_t Hi, size_t* by
 int hgnn_wgrad_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int32_t Ho, int32_t Hi,
                    float* out, int64_t ldo, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
 
+/* The rest of an EXACT fp32 step that used to be library GEMMs (additions under ABI 26, as above): the forward
+ * pre-projection and the products with one side at most 32 wide.  For all five entries: every refusal
+ * (HGNN_ERR_INVALID_ARG, or HGNN_ERR_UNSUPPORTED for a shape outside the stated ranges, + hgnn_last_error starting with
+ * the entry's name) is decided before any HIP call and touches no pointer; no atomics, no scratch memory, no allocation,
+ * no host synchronisation; grids, tiles and slices are pure functions of the shape -- never of the device -- so the same
+ * inputs give the same bits on every device and in every run.  M <= 2^31 - 1.
+ *
+ * hgnn_project_f32:  out_b[r, h] = sum_k x[r, k] * w_b[h, k]  for b = 0 and, when w1 / out1 are given (together or not
+ *   at all), b = 1: both blocks from ONE launch over the rows of x (the source and destination segment of an edge
+ *   update, as hgnn_project_f32_split3).  x [M, K] with row stride ldx; w_b [N, K] row-major with row stride ldw (a
+ *   column block W[:, c0:c1] of a first Linear is passed in place); out_b [M, N] with row stride ldo >= N.  All strides
+ *   multiples of 4 floats, all rows 16-byte aligned.  K a multiple of 16 in [16, 512], N a multiple of 16 in [16, 1024]
+ *   (anything else: HGNN_ERR_UNSUPPORTED).  Order contract: every output element is the chain
+ *       acc = 0;  acc = fmaf(x[r, k], w_b[h, k], acc)  for k ASCENDING,
+ *   every product formed once on v_mfma_f32_16x16x4_f32 (bitwise a k-ordered fmaf chain); no split-K, hence no
+ *   workspace.  One workgroup per (64 rows, block, pass of at most 256 features).  M == 0 launches nothing.
+ *
+ * The narrow products: n is the narrow width, 1 <= n <= 32; K the wide one, a multiple of 4 in [4, 1024] (anything
+ * else: HGNN_ERR_UNSUPPORTED).  fp32 VALU kernels.  Wide-side arrays ([M, K]) need 16-byte aligned rows and strides that
+ * are multiples of 4 floats; narrow-side arrays ([M, n], the [n, K] weights and wgrad result, bias, colsum) only 4-byte
+ * alignment and any stride that covers their width (tab[N, 3] with 12-byte rows is read in place).
+ * hgnn_linear_narrow_f32:  out[m, j] = bias[j] + sum_k x[m, k] * W[j, k]   (bias may be NULL).  Order: a row is shared
+ *   by P lanes, P = the largest power of two <= min(K / 4, 64) -- a function of K alone.  Lane t chains
+ *   acc = fmaf(x[m, k], W[j, k], acc) from acc = 0 over the k of its 4-float pieces t, t + P, t + 2P, ... ascending; the
+ *   P sums are added by a halving tree (v[t] += v[t + h] for h = P/2, P/4, ..., 1); the bias is added last.
+ * hgnn_outer_narrow_f32:   out[m, k] = sum_j y[m, j] * W[j, k] (+ add[m, k]).  Order: acc = 0; acc = fmaf(y[m, j],
+ *   W[j, k], acc) for j ascending from 0; add (NULL or [M, K] with out's row stride ldo) joins last with one rounding.
+ * hgnn_wgrad_narrow_f32:   out[j, k] = sum_m y[m, j] * x[m, k];  colsum[j] = sum_m y[m, j] (optional: a head's bias
+ *   gradient).  Order: the rows are split into S slices of L rows, with ng = ceil(n / 8) and
+ *       want = clamp(ceil(131072 / ((K / 4) * ng)), 1, max(1, ceil(M / 64))),  L = max(16, 16 * ceil(ceil(M / want) / 16)),
+ *       S = ceil(max(M, 1) / L);
+ *   inside a slice every element is the chain acc = fmaf(y[m, j], x[m, k], acc) (colsum: acc += y[m, j]) from acc = 0
+ *   over the slice's rows in order; the slices are added in hgnn_wgrad_f32's four-chain order, (s0 + s1) + (s2 + s3)
+ *   with the remainder on chain 0.  workspace: hgnn_wgrad_narrow_f32_workspace_bytes(M, n, K) = S * n * (K + 1) floats
+ *   of device memory, 4-byte aligned.  M == 0 writes zeros to out (and colsum). */
+int hgnn_project_f32(const float* x, int64_t ldx, int64_t M, int32_t K, const float* w0, const float* w1, int64_t ldw,
+                     int32_t N, float* out0, float* out1, int64_t ldo, hgnn_stream_t stream);
+int hgnn_linear_narrow_f32(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, int64_t ldw,
+                           const float* bias, int32_t n, float* out, int64_t ldo, hgnn_stream_t stream);
+int hgnn_outer_narrow_f32(const float* y, int64_t ldy, int64_t M, int32_t n, const float* W, int64_t ldw, int32_t K,
+                          const float* add, float* out, int64_t ldo, hgnn_stream_t stream);
+int hgnn_wgrad_narrow_f32_workspace_bytes(int64_t M, int32_t n, int32_t K, size_t* bytes);
+int hgnn_wgrad_narrow_f32(const float* y, int64_t ldy, int32_t n, const float* x, int64_t ldx, int32_t K, int64_t M,
+                          float* out, int64_t ldo, float* colsum, void* workspace, size_t workspace_bytes,
+                          hgnn_stream_t stream);
+
 /* hgnn_mlp_backward_layer_bf16: the hand-written DATA gradient of one Linear of the bf16 training path, fused with
  * what follows it in the backward:
  *   z_prev != NULL ("LayerNorm form"):  da = dz[M,K] . W[K,N];  out = dz' = dLayerNorm(act'(LN(z_prev)) * da)  with
