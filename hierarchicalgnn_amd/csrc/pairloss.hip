@@ -32,6 +32,9 @@ struct PhParams {
     float margin, scale;
 };
 
+// |E[a] - E[b]|^2 is ONE chain s = fmaf(d_k, d_k, s) over k = 0 .. D - 1 on both paths, written out: left to the
+// compiler's contraction, the float4 path became a mix of fused and packed unfused steps and the scalar path all
+// fused, so the bits of the loss depended on the alignment of E.
 template <bool V4>
 __device__ __forceinline__ float ph_dist(const float* __restrict__ E, int64_t a, int64_t b, int D) {
     float s = 0.f;
@@ -41,15 +44,15 @@ __device__ __forceinline__ float ph_dist(const float* __restrict__ E, int64_t a,
         for (int k = 0; k < D / 4; ++k) {
             const float4 u = pa[k], v = pb[k];
             const float d0 = u.x - v.x, d1 = u.y - v.y, d2 = u.z - v.z, d3 = u.w - v.w;
-            s += d0 * d0;
-            s += d1 * d1;
-            s += d2 * d2;
-            s += d3 * d3;
+            s = fmaf(d0, d0, s);
+            s = fmaf(d1, d1, s);
+            s = fmaf(d2, d2, s);
+            s = fmaf(d3, d3, s);
         }
     } else {
         for (int k = 0; k < D; ++k) {
             const float d = E[a * D + k] - E[b * D + k];
-            s += d * d;
+            s = fmaf(d, d, s);
         }
     }
     return sqrtf(s + 1e-12f);
@@ -162,7 +165,8 @@ __global__ __launch_bounds__(kBlock) void k_ph_coef(const float* __restrict__ E,
 // grad[v] = sum over the entries p of v's list of c_i (E[v] - E[other_p]), i the pair of entry p.  kPhLanes lanes share
 // one destination: lane l adds the entries l, l + kPhLanes, .. of the list in that order, then a fixed xor tree; the
 // list order is the plan's (stable by position in cat(a, b)), so the bits depend on neither the grid nor the chunk.
-// The difference is formed before it is scaled, as autograd's backward of the reference expression does.
+// The difference is formed before it is scaled, as autograd's backward of the reference expression does; each entry
+// is one fmaf on both paths, so the bits do not depend on the alignment of E either.
 constexpr int kPhLanes = 16;
 template <bool V4>
 __global__ __launch_bounds__(kBlock) void k_ph_grad(const float* __restrict__ E, int64_t N, int D,
@@ -192,16 +196,16 @@ __global__ __launch_bounds__(kBlock) void k_ph_grad(const float* __restrict__ E,
             for (int k = 0; k < HGNN_PH_MAX_DIM / 4; ++k) {
                 if (k < d4) {
                     const float4 u = row[k];
-                    acc[4 * k + 0] += c * (mine[4 * k + 0] - u.x);
-                    acc[4 * k + 1] += c * (mine[4 * k + 1] - u.y);
-                    acc[4 * k + 2] += c * (mine[4 * k + 2] - u.z);
-                    acc[4 * k + 3] += c * (mine[4 * k + 3] - u.w);
+                    acc[4 * k + 0] = fmaf(c, mine[4 * k + 0] - u.x, acc[4 * k + 0]);
+                    acc[4 * k + 1] = fmaf(c, mine[4 * k + 1] - u.y, acc[4 * k + 1]);
+                    acc[4 * k + 2] = fmaf(c, mine[4 * k + 2] - u.z, acc[4 * k + 2]);
+                    acc[4 * k + 3] = fmaf(c, mine[4 * k + 3] - u.w, acc[4 * k + 3]);
                 }
             }
         } else {
 #pragma unroll
             for (int k = 0; k < HGNN_PH_MAX_DIM; ++k)
-                if (k < D) acc[k] += c * (mine[k] - E[o * D + k]);
+                if (k < D) acc[k] = fmaf(c, mine[k] - E[o * D + k], acc[k]);
         }
     }
 #pragma unroll
