@@ -227,7 +227,8 @@ __device__ inline double wave_max(double v) {
     return v;
 }
 
-// step 2: one wave per particle over its hits (in ascending hit order: the sort is stable)
+// step 2: one wave per particle over its hits (in ascending hit order: the sort is stable).  ptmin is the minimum
+// with NaN propagation: a particle with a NaN pt has ptmin = NaN, fails `ptmin > pt_cut` and is not reconstructable
 __global__ __launch_bounds__(256) void k_te_particles(const int32_t* __restrict__ pstart,
                                                       const int32_t* __restrict__ prid,
                                                       const int32_t* __restrict__ pv, const int64_t* __restrict__ pk,
@@ -244,12 +245,12 @@ __global__ __launch_bounds__(256) void k_te_particles(const int32_t* __restrict_
         for (int j = b + lane; j < e; j += 64) {
             const int h = pv[j];
             const float v = pt[h];
-            m = v < m ? v : m;  // NaN is never selected
+            m = (v < m || v != v) ? v : m;  // NaN propagates (torch amin): once m is NaN neither test holds again
             if (primary != nullptr && primary[h] != 0) any = 1;
         }
         for (int o = 32; o > 0; o >>= 1) {
             const float v = __shfl_xor(m, o);
-            m = v < m ? v : m;
+            m = (v < m || v != v) ? v : m;  // a NaN in any lane reaches every lane
         }
         any = wave_isum(any);
         if (lane == 0) {

@@ -272,6 +272,25 @@ def cases():
     # every candidate below the size filter (the reference raises; defined here as default_response)
     add("all_filtered", hit[:40], np.arange(40), pid, pt, prim)
     add("empty", np.zeros(0), np.zeros(0), pid, pt, prim)
+
+    # NaN pt (a generator of their own: the cases above keep their bytes).  scatter_min (amin) propagates NaN, so a
+    # particle with a NaN pt is not reconstructable.  The reference's loader keeps noise hits, whose pt can be NaN:
+    # pid 0 with all-NaN pt and more than nhits_cut hits must not count in track_eff's denominator
+    rng = np.random.default_rng(20261020)
+    pid, pt, prim = random_event(rng, n_particles=40)
+    hit, cand = random_candidates(rng, pid)
+    assert (pid == 0).sum() >= 5
+    pt = pt.copy()
+    pt[pid == 0] = np.nan
+    add("pt_nan_noise", hit, cand, pid, pt, prim)
+    # one real particle with a single NaN hit, otherwise above the cut and matched with 6 of its 8 hits: were it
+    # taken for reconstructable, hit_eff would be (6/8 + 1) / 2 instead of 1
+    pid = np.concatenate([np.full(8, 11), np.full(6, 12), np.full(7, 13), np.zeros(4, np.int64)])
+    pt = np.concatenate([np.full(8, 2.0), np.full(6, 3.0), np.full(7, 0.5), np.zeros(4)]).astype(np.float32)
+    pt[5] = np.nan
+    hit = np.concatenate([np.arange(6), np.arange(8, 21)])
+    cand = np.concatenate([np.full(6, 40), np.full(6, 50), np.full(7, 60)])
+    add("pt_nan_mixed", hit, cand, pid, pt, np.ones(pid.size))
     return out
 
 

@@ -30,17 +30,38 @@ def d2_rows(x, lo, hi):
     return acc
 
 
-def core2(x, min_samples, chunk=512):
+MUTANTS = ("rank_lo", "rank_hi", "tie_maxmin", "last_point", "last_slice", "binary", "lambda_denorm")
+
+
+def slice_layout(n, tile=256):
+    """(slices, slice_len) of the candidate slicing of one Boruvka round (csrc/hdbscan.hip hdb_layout): at most 16
+    slices, each a whole number of 256-point tiles, enough of them for 1024 workgroups"""
+    blocks = -(-n // tile)
+    s = min(max(-(-1024 // blocks), 1), 16)
+    slice_len = -(-(-(-n // s)) // tile) * tile
+    return -(-n // slice_len), slice_len
+
+
+def core2(x, min_samples, chunk=512, mutant=None):
+    """``mutant`` (tests only, tests/test_hdbscan_exact_ref.py): rank_lo / rank_hi take rank k-2 / k instead of
+    k-1; last_point never offers the point N-1 as a candidate (every rank is taken among the other N-1 values)"""
     n = x.shape[0]
+    r = min_samples - 1 + {"rank_lo": -1, "rank_hi": 1}.get(mutant, 0)
+    cols = n - 1 if mutant == "last_point" else n
+    r = min(r, cols - 1)
+    assert 0 <= r < cols, "the mutant does not apply"
     out = np.empty(n, np.float32)
     for lo in range(0, n, chunk):
         hi = min(n, lo + chunk)
-        out[lo:hi] = np.partition(d2_rows(x, lo, hi), min_samples - 1, axis=1)[:, min_samples - 1]
+        out[lo:hi] = np.partition(d2_rows(x, lo, hi)[:, :cols], r, axis=1)[:, r]
     return out
 
 
-def mst(x, c2):
-    """Prim with every choice made under the strict total order (w2, min, max): the order is total, so the minimum
+def mst(x, c2, mutant=None):
+    """``mutant`` (tests only): tie_maxmin orders equal weights by (max, min); last_slice never offers the points of
+    the last candidate slice (slice_layout), so an edge between two of them is never seen.
+
+    Prim with every choice made under the strict total order (w2, min, max): the order is total, so the minimum
     spanning tree is unique and this is the tree Kruskal under the same order builds.  Returns (edges [N-1, 2] with
     min first, w2 [N-1]) sorted by (w2, min, max)."""
     n = x.shape[0]
@@ -53,9 +74,19 @@ def mst(x, c2):
     w2 = np.empty(n - 1, np.float32)
     cur = 0
     in_tree[0] = True
+    cutoff = n
+    if mutant == "last_slice":
+        slices, slice_len = slice_layout(n)
+        cutoff = (slices - 1) * slice_len
+        assert cutoff > 0, "the mutant does not apply"
     for e in range(n - 1):
         w = np.maximum(np.maximum(d2_rows(x, cur, cur + 1)[0], c2), c2[cur])
-        k = np.minimum(ids, cur) * n + np.maximum(ids, cur)
+        if cur >= cutoff:
+            w[cutoff:] = np.inf
+        if mutant == "tie_maxmin":
+            k = np.maximum(ids, cur) * n + np.minimum(ids, cur)
+        else:
+            k = np.minimum(ids, cur) * n + np.maximum(ids, cur)
         better = (w < bw) | ((w == bw) & (k < bk))
         better &= ~in_tree
         bw[better] = w[better]
@@ -65,7 +96,7 @@ def mst(x, c2):
         assert np.isfinite(m), "non-finite input"
         tie = np.flatnonzero(cand == m)
         nxt = tie[np.argmin(bk[tie])]
-        edges[e] = (bk[nxt] // n, bk[nxt] % n)
+        edges[e] = sorted((bk[nxt] // n, bk[nxt] % n))
         w2[e] = m
         in_tree[nxt] = True
         cur = int(nxt)
@@ -73,12 +104,15 @@ def mst(x, c2):
     return edges[order], w2[order]
 
 
-def _lambda(w):
-    return 1.0 / np.sqrt(np.float64(w)) if w > 0 else LAMBDA_DUP
+def _lambda(w, dup=LAMBDA_DUP):
+    return 1.0 / np.sqrt(np.float64(w)) if w > 0 else dup
 
 
-def tree_labels(edges, w2, n, min_cluster_size, return_info=False):
-    """dendrogram with multi-way levels -> condensed tree -> EOM -> labels, from MST edges sorted by w2"""
+def tree_labels(edges, w2, n, min_cluster_size, return_info=False, mutant=None):
+    """dendrogram with multi-way levels -> condensed tree -> EOM -> labels, from MST edges sorted by w2.
+    ``mutant`` (tests only): binary makes every edge a level of its own; lambda_denorm takes lambda of w2 = 0 as
+    1 / sqrt(smallest positive float32)"""
+    dup = 1.0 / np.sqrt(np.float64(2.0 ** -149)) if mutant == "lambda_denorm" else LAMBDA_DUP
     mcs = int(min_cluster_size)
     m = len(w2)
     assert m == n - 1
@@ -99,6 +133,8 @@ def tree_labels(edges, w2, n, min_cluster_size, return_info=False):
         f = e
         while f < m and w2[f] == w2[e]:
             f += 1
+        if mutant == "binary":
+            f = e + 1
         old = {}
         for a, b in edges[e:f]:
             ra, rb = find(int(a)), find(int(b))
@@ -138,7 +174,7 @@ def tree_labels(edges, w2, n, min_cluster_size, return_info=False):
         if node < n:                  # only when n == 1
             fell[node] = c
             continue
-        lam = _lambda(level[node])
+        lam = _lambda(level[node], dup)
         kids = children[node]
         big = [k for k in kids if size[k] >= mcs]
         for k in kids:
@@ -199,14 +235,14 @@ def canonical(raw):
     return out
 
 
-def hdbscan(x, min_cluster_size=5, min_samples=None, return_all=False):
+def hdbscan(x, min_cluster_size=5, min_samples=None, return_all=False, mutant=None):
     x = np.ascontiguousarray(x, dtype=np.float32)
     n = x.shape[0]
     ms = int(min_cluster_size if min_samples is None else min_samples)
     assert n >= min_cluster_size and 1 <= ms <= n
-    c2 = core2(x, ms)
-    edges, w2 = mst(x, c2)
-    labels, info = tree_labels(edges, w2, n, min_cluster_size, return_info=True)
+    c2 = core2(x, ms, mutant=mutant)
+    edges, w2 = mst(x, c2, mutant=mutant)
+    labels, info = tree_labels(edges, w2, n, min_cluster_size, return_info=True, mutant=mutant)
     if return_all:
         return labels, edges, w2, c2, info
     return labels

@@ -51,8 +51,22 @@ def test_restatement_matches_reference(cs):
 def test_fixture_covers_the_contract():
     names = {c["name"] for c in CASES}
     for must in ("hash_tie_C6000", "size_filter_fp32_boundary", "pt_cut_fp32_boundary", "duplicates",
-                 "pids_40bit_signed", "no_match_mixed", "no_match_after_filter", "zero_truth_nan", "all_filtered"):
+                 "pids_40bit_signed", "no_match_mixed", "no_match_after_filter", "zero_truth_nan", "all_filtered",
+                 "pt_nan_noise", "pt_nan_mixed"):
         assert must in names
+    # NaN pt propagates into ptmin: not reconstructable, neither in the mask nor in n_truth
+    noise = next(c for c in CASES if c["name"] == "pt_nan_noise")
+    sel = noise["pid"] == 0
+    assert sel.sum() >= noise["params"][1] and np.isnan(noise["pt"][sel]).all()
+    assert not np.isnan(noise["pt"][~sel]).any()
+    finite = dict(noise, pt=np.where(sel, np.float32(5.0), noise["pt"]))
+    assert restate(finite)["n_truth"] == restate(noise)["n_truth"] + 1
+    assert restate(finite)["track_eff"] != restate(noise)["track_eff"] == noise["expected"][0]
+    mixed = next(c for c in CASES if c["name"] == "pt_nan_mixed")
+    assert np.isnan(mixed["pt"]).sum() == 1 and int(mixed["status"]) == 0
+    r = restate(mixed)
+    assert (r["n_kept"], r["n_mask"], r["n_truth"], r["hit_eff"]) == (3, 1, 1, 1.0)
+    assert restate(dict(mixed, pt=np.nan_to_num(mixed["pt"], nan=2.0)))["hit_eff"] == (6 / 8 + 1) / 2
     tie = restate(next(c for c in CASES if c["name"] == "hash_tie_C6000"))
     assert tie["track_eff"] == 2.0 and tie["n_kept"] == 2
     assert np.isnan(restate(next(c for c in CASES if c["name"] == "zero_truth_nan"))["track_eff"])

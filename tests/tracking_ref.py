@@ -8,6 +8,9 @@ cut compare in float32, everything after the contingency table in float64.
 import numpy as np
 
 KEYS = ("track_eff", "track_pur", "hit_eff", "hit_pur")
+# wrong readings of the contract, for tests/test_tracking_exact_ref.py: the six comparisons with the other sign, the
+# hash tie to the lower label, duplicate pairs counted once, the size filter compared in float64
+MUTANTS = ("size_gt", "col_gt", "row_gt", "kept_ge", "pt_ge", "nhits_gt", "tie_low", "dup_once", "size_f64")
 
 
 def cluster_hash(C: int) -> np.ndarray:
@@ -28,16 +31,27 @@ def _default(C, P, n_match=0, n_kept=0):
                 n_truth=0, n_cand=C, n_part=P, n_match=n_match)
 
 
-def track_eval(hit, cand, pid, pt, primary=None, pt_cut=1.0, nhits_cut=5, majority_cut=0.5):
-    """primary: None (the reference's primary=False) or per-hit flags (primary=True)"""
+def track_eval(hit, cand, pid, pt, primary=None, pt_cut=1.0, nhits_cut=5, majority_cut=0.5, mutant=None):
+    """primary: None (the reference's primary=False) or per-hit flags (primary=True).  A particle with a NaN pt has
+    ptmin = NaN (np.minimum propagates it, as torch's amin does in the fixture generator) and is not
+    reconstructable.  ``mutant``: one of MUTANTS (tests only)"""
+    assert mutant is None or mutant in MUTANTS
     hit, cand = np.asarray(hit, np.int64), np.asarray(cand, np.int64)
     pid, pt = np.asarray(pid, np.int64), np.asarray(pt, np.float32)
     if hit.size and (hit.min() < 0 or hit.max() >= pid.size):
         raise ValueError("hit id out of range")
     # 1. candidate size filter (float32 comparison), dense relabel in ascending label order
+    if hit.size and mutant == "dup_once":
+        pairs = np.unique(np.stack([hit, cand], 1), axis=0)
+        hit, cand = pairs[:, 0], pairs[:, 1]
     if hit.size:
         _, inv, cnt = np.unique(cand, return_inverse=True, return_counts=True)
-        keep = cnt[inv].astype(np.float32) >= np.float32(nhits_cut * majority_cut)
+        if mutant == "size_f64":
+            keep = cnt[inv].astype(np.float64) >= nhits_cut * majority_cut
+        elif mutant == "size_gt":
+            keep = cnt[inv].astype(np.float32) > np.float32(nhits_cut * majority_cut)
+        else:
+            keep = cnt[inv].astype(np.float32) >= np.float32(nhits_cut * majority_cut)
         hit, cand = hit[keep], cand[keep]
     # 2. particles
     opid, p_of_hit, nhits = np.unique(pid, return_inverse=True, return_counts=True)
@@ -47,7 +61,8 @@ def track_eval(hit, cand, pid, pt, primary=None, pt_cut=1.0, nhits_cut=5, majori
     _, c_of_pair = np.unique(cand, return_inverse=True)
     C = int(c_of_pair.max()) + 1
     ptmin = np.full(P, np.inf, np.float32)
-    np.minimum.at(ptmin, p_of_hit, pt)
+    with np.errstate(invalid="ignore"):
+        np.minimum.at(ptmin, p_of_hit, pt)        # propagates NaN
     prim = np.zeros(P, bool)
     if primary is not None:
         prim[p_of_hit[np.asarray(primary) != 0]] = True
@@ -57,24 +72,28 @@ def track_eval(hit, cand, pid, pt, primary=None, pt_cut=1.0, nhits_cut=5, majori
     rows, cols, n = uk // C, uk % C, n.astype(np.float64)
     col = np.bincount(c_of_pair, minlength=C).astype(np.float64)
     # 4-5. hashing tie-break and matching
-    nh = n * cluster_hash(C)[cols]
+    nh = n * (cluster_hash(C)[::-1] if mutant == "tie_low" else cluster_hash(C))[cols]
     rowmax = np.zeros(P)
     np.maximum.at(rowmax, rows, nh)
     nhits_f = nhits.astype(np.float64)
-    match = (n >= majority_cut * col[cols]) & (n >= majority_cut * nhits_f[rows]) & (nh == rowmax[rows])
+    by_col = n > majority_cut * col[cols] if mutant == "col_gt" else n >= majority_cut * col[cols]
+    by_row = n > majority_cut * nhits_f[rows] if mutant == "row_gt" else n >= majority_cut * nhits_f[rows]
+    match = by_col & by_row & (nh == rowmax[rows])
     n_match = int(match.sum())
     if n_match == 0:
         return _default(C, P)
     mr, mc, mn = rows[match], cols[match], n[match]
     # 6. match filter
-    kf = (mn > majority_cut * nhits_cut) & (opid[mr] != 0)
+    big = mn >= majority_cut * nhits_cut if mutant == "kept_ge" else mn > majority_cut * nhits_cut
+    kf = big & (opid[mr] != 0)
     n_kept = int(kf.sum())
     if n_kept == 0:
         return _default(C, P, n_match)
     kr, kc, kn = mr[kf], mc[kf], mn[kf]
     # 7. metrics
-    mask = (ptmin[kr] > np.float32(pt_cut)) & (nhits[kr] >= nhits_cut)
-    truth = (ptmin > np.float32(pt_cut)) & (nhits >= nhits_cut)
+    above = ptmin >= np.float32(pt_cut) if mutant == "pt_ge" else ptmin > np.float32(pt_cut)
+    truth = above & (nhits > nhits_cut if mutant == "nhits_gt" else nhits >= nhits_cut)
+    mask = truth[kr]
     if primary is not None:
         mask &= prim[kr]
         truth &= prim
