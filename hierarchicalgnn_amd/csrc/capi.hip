@@ -30,6 +30,7 @@ static const struct {
     {"k1_waves", &g_opt_k1_waves, INT_MIN, INT_MAX, nullptr},
 #endif
     {"mlp_ablate", &g_opt_mlp_ablate, INT_MIN, INT_MAX, nullptr},  // stored & 31
+    {"mlp_act_switch", &g_opt_mlp_act_switch, 0, 1, "takes 0 or 1"},
     {"mlp_split_variant", &g_opt_mlp_split_variant, INT_MIN, INT_MAX, nullptr},
     {"mlp_split3_rows128", &f3::g_opt_split3_rows128, 0, 2,
      "takes 0 or 1 (2 = experimental tile, needs HGNN_EXPERIMENTAL=1)"},

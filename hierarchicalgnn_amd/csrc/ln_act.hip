@@ -46,7 +46,9 @@ __device__ __forceinline__ void st_row4(unsigned short* p, f32x4 v) {
     *(u16x4*)p = o;
 }
 
-template <int NV, bool BACKWARD, typename T, int LPR = 16>
+// LN = false (hgnn_act_rows_*: a layer of a network without LayerNorm): no statistics, gamma / beta are not read;
+// forward a = act(z), backward dz = da * act'(z) with ONE column sum (dbias), partials [HGNN_LN_ACT_BLOCKS][W]
+template <int NV, bool BACKWARD, typename T, int LPR = 16, bool LN = true>
 __global__ __launch_bounds__(256) void k_ln_act(const T* __restrict__ z, const T* __restrict__ da,
                                                 long long M, const float* __restrict__ gamma,
                                                 const float* __restrict__ beta, int act, float eps,
@@ -62,10 +64,12 @@ __global__ __launch_bounds__(256) void k_ln_act(const T* __restrict__ z, const T
     const int l16 = lane % LPR;  // this lane's 4-float column slot within a vector
     const int rg = lane / LPR;   // row within the wave's group of RPW
     f32x4 gm[NV], bt[NV];
+    if constexpr (LN) {
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        gm[v] = *(const f32x4*)(gamma + (v * LPR + l16) * 4);
-        bt[v] = *(const f32x4*)(beta + (v * LPR + l16) * 4);
+        for (int v = 0; v < NV; ++v) {
+            gm[v] = *(const f32x4*)(gamma + (v * LPR + l16) * 4);
+            bt[v] = *(const f32x4*)(beta + (v * LPR + l16) * 4);
+        }
     }
     f32x4 s_dg[BACKWARD ? NV : 1], s_db[BACKWARD ? NV : 1], s_dz[BACKWARD ? NV : 1];
     if constexpr (BACKWARD) {
@@ -87,6 +91,28 @@ __global__ __launch_bounds__(256) void k_ln_act(const T* __restrict__ z, const T
         if constexpr (BACKWARD) {
 #pragma unroll
             for (int v = 0; v < NV; ++v) g[v] = ld_row4(da + off + v * VS);
+        }
+        if constexpr (!LN) {
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                f32x4 o;
+                float* ov = (float*)&o;
+                const float* xv = (const float*)&x[v];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if constexpr (BACKWARD) {
+                        const float a = act == HGNN_ACT_TANH ? fast_tanh(xv[c]) : 0.f;
+                        ov[c] = valid ? ((const float*)&g[v])[c] * act_grad(xv[c], a, act) : 0.f;
+                    } else {
+                        ov[c] = act_apply(xv[c], act);
+                    }
+                }
+                if (valid) st_row4(out + off + v * VS, o);
+                if constexpr (BACKWARD) {
+                    s_dz[v].x += o.x; s_dz[v].y += o.y; s_dz[v].z += o.z; s_dz[v].w += o.w;
+                }
+            }
+            continue;
         }
         const float mean = row_sum<LPR>(s) * inv_w;
         float q = 0.f;
@@ -151,7 +177,21 @@ __global__ __launch_bounds__(256) void k_ln_act(const T* __restrict__ z, const T
             }
         }
     }
-    if constexpr (BACKWARD) {
+    if constexpr (BACKWARD && !LN) {
+        // the one column sum: row groups of the wave, then the 4 waves through LDS
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float t = ((float*)&s_dz[v])[c];
+#pragma unroll
+                for (int o = LPR; o < 64; o <<= 1) t += __shfl_xor(t, o);
+                if (rg == 0) red[wave * W + (v * LPR + l16) * 4 + c] = t;
+            }
+        __syncthreads();
+        for (int i = tid; i < W; i += 256)
+            partials[(size_t)blockIdx.x * W + i] = (red[i] + red[W + i]) + (red[2 * W + i] + red[3 * W + i]);
+    } else if constexpr (BACKWARD) {
         // column partials: the wave's 4 row groups (lanes l16, l16+16, ...), then the 4 waves through LDS
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
@@ -172,21 +212,21 @@ __global__ __launch_bounds__(256) void k_ln_act(const T* __restrict__ z, const T
     }
 }
 
-template <bool BACKWARD, typename T>
+template <bool BACKWARD, typename T, bool LN = true>
 static int launch_ln_act(const T* z, const T* da, int64_t M, int W, const float* gamma, const float* beta,
                          int act, float eps, T* out, float* partials, hipStream_t s) {
     const unsigned grid = BACKWARD ? (unsigned)kLnActBlocks
                                    : (unsigned)(ceil_div(M, 16) < 4096 ? ceil_div(M, 16) : 4096);
     if (W == 1024) {   // one row per wave (64 lanes x 4 vectors): the hidden width at latent 512
-        k_ln_act<4, BACKWARD, T, 64><<<grid, 256, 0, s>>>(z, da, M, gamma, beta, act, eps, out, partials);
+        k_ln_act<4, BACKWARD, T, 64, LN><<<grid, 256, 0, s>>>(z, da, M, gamma, beta, act, eps, out, partials);
         HGNN_CHECK_HIP(hipGetLastError());
         return HGNN_OK;
     }
     switch (W / 64) {
-        case 1: k_ln_act<1, BACKWARD, T><<<grid, 256, 0, s>>>(z, da, M, gamma, beta, act, eps, out, partials); break;
-        case 2: k_ln_act<2, BACKWARD, T><<<grid, 256, 0, s>>>(z, da, M, gamma, beta, act, eps, out, partials); break;
-        case 4: k_ln_act<4, BACKWARD, T><<<grid, 256, 0, s>>>(z, da, M, gamma, beta, act, eps, out, partials); break;
-        case 8: k_ln_act<8, BACKWARD, T><<<grid, 256, 0, s>>>(z, da, M, gamma, beta, act, eps, out, partials); break;
+        case 1: k_ln_act<1, BACKWARD, T, 16, LN><<<grid, 256, 0, s>>>(z, da, M, gamma, beta, act, eps, out, partials); break;
+        case 2: k_ln_act<2, BACKWARD, T, 16, LN><<<grid, 256, 0, s>>>(z, da, M, gamma, beta, act, eps, out, partials); break;
+        case 4: k_ln_act<4, BACKWARD, T, 16, LN><<<grid, 256, 0, s>>>(z, da, M, gamma, beta, act, eps, out, partials); break;
+        case 8: k_ln_act<8, BACKWARD, T, 16, LN><<<grid, 256, 0, s>>>(z, da, M, gamma, beta, act, eps, out, partials); break;
         default:
             set_error("hgnn_ln_act: width %d has no instantiation (64, 128, 256, 512, 1024)", W);
             return HGNN_ERR_UNSUPPORTED;
@@ -204,7 +244,7 @@ static int check_ln_act(const void* z, int64_t M, int W, const void* gamma, cons
     HGNN_REQUIRE(M >= 0, "%s: bad M", who);
     HGNN_REQUIRE(W == 64 || W == 128 || W == 256 || W == 512 || W == 1024,
                  "%s: width must be 64, 128, 256, 512 or 1024 (got %d)", who, W);
-    HGNN_REQUIRE(act >= HGNN_ACT_NONE && act <= HGNN_ACT_RELU, "%s: unknown activation code %d", who, act);
+    HGNN_REQUIRE(act >= HGNN_ACT_NONE && act <= HGNN_ACT_LAST, "%s: unknown activation code %d", who, act);
     if (M == 0) return HGNN_OK;
     HGNN_REQUIRE(z != nullptr && gamma != nullptr && beta != nullptr && out != nullptr, "%s: NULL pointer", who);
     HGNN_REQUIRE((uintptr_t)z % 16 == 0 && (uintptr_t)gamma % 16 == 0 && (uintptr_t)beta % 16 == 0 &&
@@ -251,4 +291,36 @@ extern "C" int hgnn_ln_act_backward_bf16(const void* z, const void* grad_out, in
                  "hgnn_ln_act_backward_bf16: grad_out is NULL or not 16-byte aligned");
     return launch_ln_act<true, unsigned short>((const unsigned short*)z, (const unsigned short*)grad_out, M, W, gamma,
                                                beta, act, eps, (unsigned short*)grad_z, partials, (hipStream_t)stream);
+}
+
+static int check_act_rows(const void* z, int64_t M, int W, int act, const void* out, const char* who) {
+    HGNN_REQUIRE(M >= 0, "%s: bad M", who);
+    HGNN_REQUIRE(W == 64 || W == 128 || W == 256 || W == 512 || W == 1024,
+                 "%s: width must be 64, 128, 256, 512 or 1024 (got %d)", who, W);
+    HGNN_REQUIRE(act >= HGNN_ACT_NONE && act <= HGNN_ACT_LAST, "%s: unknown activation code %d", who, act);
+    if (M == 0) return HGNN_OK;
+    HGNN_REQUIRE(z != nullptr && out != nullptr, "%s: NULL pointer", who);
+    HGNN_REQUIRE((uintptr_t)z % 16 == 0 && (uintptr_t)out % 16 == 0, "%s: pointers must be 16-byte aligned", who);
+    return HGNN_OK;
+}
+
+extern "C" int hgnn_act_rows_forward_f32(const float* z, int64_t M, int32_t W, int32_t act, float* out,
+                                         hgnn_stream_t stream) {
+    const int rc = check_act_rows(z, M, W, act, out, "hgnn_act_rows_forward_f32");
+    if (rc != HGNN_OK || M == 0) return rc;
+    return launch_ln_act<false, float, false>(z, nullptr, M, W, nullptr, nullptr, act, 0.f, out, nullptr,
+                                              (hipStream_t)stream);
+}
+
+extern "C" int hgnn_act_rows_backward_f32(const float* z, const float* grad_out, int64_t M, int32_t W, int32_t act,
+                                          float* grad_z, float* partials, hgnn_stream_t stream) {
+    const int rc = check_act_rows(z, M, W, act, grad_z, "hgnn_act_rows_backward_f32");
+    if (rc != HGNN_OK) return rc;
+    HGNN_REQUIRE(partials != nullptr && (uintptr_t)partials % 16 == 0,
+                 "hgnn_act_rows_backward_f32: partials must be a 16-byte aligned [HGNN_LN_ACT_BLOCKS][W] buffer");
+    HGNN_REQUIRE(M == 0 || (grad_out != nullptr && (uintptr_t)grad_out % 16 == 0),
+                 "hgnn_act_rows_backward_f32: grad_out is NULL or not 16-byte aligned");
+    // M == 0 still runs: every workgroup writes its (zero) partials
+    return launch_ln_act<true, float, false>(z, grad_out, M, W, nullptr, nullptr, act, 0.f, grad_z, partials,
+                                             (hipStream_t)stream);
 }

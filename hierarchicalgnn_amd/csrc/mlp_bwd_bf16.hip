@@ -390,7 +390,7 @@ extern "C" int hgnn_mlp_backward_layer_bf16(const void* dz, int64_t M, int32_t K
     HGNN_REQUIRE(!ln || (ln_w != nullptr && ln_b != nullptr && partials != nullptr && skip == nullptr),
                  "hgnn_mlp_backward_layer_bf16: the LayerNorm form needs ln_w, ln_b, partials and no skip");
     HGNN_REQUIRE(ln || (a_prev == nullptr && partials == nullptr), "hgnn_mlp_backward_layer_bf16: a_prev / partials belong to the LayerNorm form");
-    HGNN_REQUIRE(act >= HGNN_ACT_NONE && act <= HGNN_ACT_RELU, "hgnn_mlp_backward_layer_bf16: unknown activation code %d", act);
+    HGNN_REQUIRE(act >= HGNN_ACT_NONE && act <= HGNN_ACT_LAST, "hgnn_mlp_backward_layer_bf16: unknown activation code %d", act);
     if (M == 0 && !ln) return HGNN_OK;
     HGNN_REQUIRE(M == 0 || (dz != nullptr && Wt_frag != nullptr && out != nullptr), "hgnn_mlp_backward_layer_bf16: NULL pointer");
     HGNN_REQUIRE((uintptr_t)dz % 16 == 0 && (uintptr_t)Wt_frag % 16 == 0 && (uintptr_t)z_prev % 8 == 0 &&

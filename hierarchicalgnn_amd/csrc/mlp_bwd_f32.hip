@@ -309,6 +309,7 @@ static int launch(const Args& a, hipStream_t s) {
     switch (a.act) {   // the hidden layers of every network are GELU; Tanh closes the two-layer ones
         case HGNN_ACT_GELU: return launch_act<NT, MINW, true, HGNN_ACT_GELU>(a, s);
         case HGNN_ACT_TANH: return launch_act<NT, MINW, true, HGNN_ACT_TANH>(a, s);
+        case HGNN_ACT_SILU: return launch_act<NT, MINW, true, HGNN_ACT_SILU>(a, s);   // hidden_activation: SiLU
     }
     return launch_act<NT, MINW, true, -1>(a, s);
 }
@@ -337,7 +338,7 @@ extern "C" int hgnn_mlp_backward_layer_f32(const float* dz, int64_t M, int32_t K
     HGNN_REQUIRE(!ln || (ln_w != nullptr && ln_b != nullptr && partials != nullptr && skip == nullptr),
                  "%s: the LayerNorm form needs ln_w, ln_b, partials and no skip", fn);
     HGNN_REQUIRE(ln || (a_prev == nullptr && partials == nullptr), "%s: a_prev / partials belong to the LayerNorm form", fn);
-    HGNN_REQUIRE(act >= HGNN_ACT_NONE && act <= HGNN_ACT_RELU, "%s: unknown activation code %d", fn, act);
+    HGNN_REQUIRE(act >= HGNN_ACT_NONE && act <= HGNN_ACT_LAST, "%s: unknown activation code %d", fn, act);
     if (M == 0 && !ln) return HGNN_OK;
     HGNN_REQUIRE(M == 0 || (dz != nullptr && Wt != nullptr && out != nullptr), "%s: NULL pointer", fn);
     HGNN_REQUIRE((uintptr_t)dz % 16 == 0 && (uintptr_t)Wt % 16 == 0 && (uintptr_t)z_prev % 16 == 0 &&

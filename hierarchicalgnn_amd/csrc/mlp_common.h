@@ -32,16 +32,69 @@ __device__ __forceinline__ float fast_tanh(float x) {
     return __builtin_copysignf(r, x);
 }
 
+// SiLU, LeakyReLU, ELU, Sigmoid (HGNN_ACT_SILU .. HGNN_ACT_SIGMOID: the torch.nn classes at their constructor
+// defaults).  u = 2^-24; v_exp_f32 and v_rcp_f32 are taken at 1 ulp (|rel| <= 2u); tests/act_ref.py emulates these
+// forms in float32 and proves the bounds (tests/test_act_ref.py).
+//   sigmoid(x)  = 1 / (1 + 2^(-x log2 e)): no cancellation at either end (x -> -inf: 2^(..) -> +inf, rcp -> 0;
+//       x -> +inf: 1 / (1 + 0)).  The rounded exponent x log2 e costs 1.25 |x| u relative in the power (|x| u the
+//       product's rounding, 0.22 |x| u the float32 constant), hence |rel error| <= (1.25 |x| + 6) u, |abs error| <= 4 u;
+//       below x = -87 the result is 0 or denormal against a true value < 2^-125.
+//   silu(x)     = x * sigmoid(x): |rel error| <= (1.25 |x| + 7) u, |abs error| <= 8 u.
+//   sigmoid'(x) = e r^2 with e = 2^(-|x| log2 e) in (0, 1], r = 1 / (1 + e): the symmetric form, no 1 - s.
+//       |rel error| <= (1.25 |x| + 9) u, |abs error| <= 3 u.
+//   silu'(x)    = s + x e r^2, s = x >= 0 ? r : e r  (sigmoid from the same e, r): |abs error| <= 12 u on a value in
+//       [-0.1, 1.1]; relative to max(|silu'|, 1/8): <= 64 u (silu' crosses zero at x = -1.2785).
+//   leaky(x)    = x > 0 ? x : 0.01f x: one rounding; against the float64 slope 0.01 |rel error| <= 2 u (0.01f itself is
+//       0.01 (1 + 2.2e-8)).  leaky' = x > 0 ? 1 : 0.01f.
+//   elu(x)      = x > 0 ? x : expm1(x).  exp(x) - 1 cancels below |x| ~ 1: for -1/4 < x <= 0 it is the Taylor
+//       polynomial x (1 + x/2 + x^2/6 + x^3/24 + x^4/120 + x^5/720) (truncation x^6/5040 <= 4.9e-8 relative at 1/4,
+//       Horner rounding <= 3 u), else 2^(x log2 e) - 1, whose subtraction is exact for x <= -1/4 (Sterbenz or a result
+//       in [-1, -1/2) with the power's own ulp) and inherits the power's absolute error <= (1.25 |x| + 2) u e^x <= 3 u:
+//       |rel error| <= 16 u everywhere (worst at x = -1/4: 3 u e^-1/4 / (1 - e^-1/4) < 11 u), down to |x| = 2^-149.
+//   elu'(x)     = x > 0 ? 1 : 2^(x log2 e): the power itself, never elu + 1 of a cancelled value; |rel error|
+//       <= (1.25 |x| + 3) u (the power at 1 ulp off the correctly rounded value: 1.5 ulp = 3 u).
+__device__ __forceinline__ float fast_sigmoid(float x) {
+    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
+}
+
+// sigmoid(x) and sigmoid'(x) from one v_exp_f32 and one v_rcp_f32 on the |x| side
+__device__ __forceinline__ void sigmoid_val_grad(float x, float& s, float& ds) {
+    const float e = __builtin_amdgcn_exp2f(-1.44269504088896341f * __builtin_fabsf(x));
+    const float r = __builtin_amdgcn_rcpf(1.0f + e);
+    const float er = e * r;
+    s = x >= 0.f ? r : er;
+    ds = er * r;
+}
+
+// expm1 of xn <= 0 given e = exp(xn)
+__device__ __forceinline__ float elu_neg(float xn, float e) {
+    float p = fmaf(1.0f / 720.0f, xn, 1.0f / 120.0f);
+    p = fmaf(p, xn, 1.0f / 24.0f);
+    p = fmaf(p, xn, 1.0f / 6.0f);
+    p = fmaf(p, xn, 0.5f);
+    p = fmaf(p, xn, 1.0f);
+    return xn > -0.25f ? xn * p : e - 1.0f;
+}
+
 __device__ __forceinline__ float act_apply(float x, int act) {
     switch (act) {
         case HGNN_ACT_GELU: return 0.5f * x * (1.0f + fast_erf(x * 0.70710678118654752440f));
         case HGNN_ACT_TANH: return fast_tanh(x);
         case HGNN_ACT_RELU: return x > 0.f ? x : 0.f;
+        case HGNN_ACT_SILU: return x * fast_sigmoid(x);
+        case HGNN_ACT_LEAKY_RELU: return x > 0.f ? x : 0.01f * x;
+        case HGNN_ACT_ELU: {
+            const float xn = __builtin_fminf(x, 0.f);
+            const float en = elu_neg(xn, __builtin_amdgcn_exp2f(1.44269504088896341f * xn));
+            return x > 0.f ? x : en;
+        }
+        case HGNN_ACT_SIGMOID: return fast_sigmoid(x);
         default: return x;
     }
 }
 
-// exact-GELU derivative: Phi(y) + y * phi(y)
+// exact-GELU derivative: Phi(y) + y * phi(y).  `a` = act(y) is read by Tanh only; the codes above ReLU take their
+// derivative from y alone
 __device__ __forceinline__ float act_grad(float y, float a, int act) {
     switch (act) {
         case HGNN_ACT_GELU: {
@@ -51,6 +104,21 @@ __device__ __forceinline__ float act_grad(float y, float a, int act) {
         }
         case HGNN_ACT_TANH: return fmaf(-a, a, 1.0f);
         case HGNN_ACT_RELU: return y > 0.f ? 1.0f : 0.f;
+        case HGNN_ACT_SILU: {
+            float s, ds;
+            sigmoid_val_grad(y, s, ds);
+            return fmaf(y, ds, s);
+        }
+        case HGNN_ACT_LEAKY_RELU: return y > 0.f ? 1.0f : 0.01f;
+        case HGNN_ACT_ELU: {
+            const float e = __builtin_amdgcn_exp2f(1.44269504088896341f * __builtin_fminf(y, 0.f));
+            return y > 0.f ? 1.0f : e;
+        }
+        case HGNN_ACT_SIGMOID: {
+            float s, ds;
+            sigmoid_val_grad(y, s, ds);
+            return ds;
+        }
         default: return 1.0f;
     }
 }
@@ -85,6 +153,29 @@ __device__ __forceinline__ void act_val_grad(float y, int act, float& val, float
         case HGNN_ACT_RELU:
             val = y > 0.f ? y : 0.f;
             grad = y > 0.f ? 1.0f : 0.f;
+            return;
+        case HGNN_ACT_SILU: {
+            float s, ds;
+            sigmoid_val_grad(y, s, ds);
+            val = y * s;
+            grad = fmaf(y, ds, s);
+            return;
+        }
+        case HGNN_ACT_LEAKY_RELU:
+            val = y > 0.f ? y : 0.01f * y;
+            grad = y > 0.f ? 1.0f : 0.01f;
+            return;
+        case HGNN_ACT_ELU: {
+            // one power: exp(min(y, 0)) is the derivative and feeds the value's far branch
+            const float yn = __builtin_fminf(y, 0.f);
+            const float e = __builtin_amdgcn_exp2f(1.44269504088896341f * yn);
+            const float en = elu_neg(yn, e);
+            val = y > 0.f ? y : en;
+            grad = y > 0.f ? 1.0f : e;
+            return;
+        }
+        case HGNN_ACT_SIGMOID:
+            sigmoid_val_grad(y, val, grad);
             return;
         default:
             val = y;

@@ -40,6 +40,12 @@
 
 namespace hgnn {
 
+int g_opt_mlp_act_switch = 0;   // hgnn_set_option("mlp_act_switch", 1): MEASUREMENT, every multi-layer fp32 launch takes the
+                                // runtime-switch instantiation (ACT = -1) although its combination has one of its own
+                                // (tools/bench_mlp_activations.py times the switch with it).  Same source arithmetic; the
+                                // same bits on this file's kernels.  On the split-bf16 kernel the compiler may contract an
+                                // inlined activation's last product into the hi / mid split that follows it: last-bit
+                                // differences in the hidden planes, both inside the kernel's bar
 int g_opt_mlp_ablate = 0;   // set through hgnn_set_option("mlp_ablate", bits): DIAGNOSTIC, wrong results
 
 struct MlpArgs {
@@ -117,6 +123,19 @@ __device__ __forceinline__ void layernorm_act(f32x4 (&acc)[NT], const float* __r
         v.z = act_apply(v.z, code);
         v.w = act_apply(v.w, code);
         acc[T] = v;
+    }
+}
+
+// a LayerNorm-less layer (PLAIN kernels, hgnn_mlp_forward_f32_plain): act on the bias-initialised accumulators, no
+// statistics.  Zero-padded features of a narrow last layer come out as act(0); its store masks them
+template <int NT>
+__device__ __forceinline__ void act_only(f32x4 (&acc)[NT], int act) {
+#pragma unroll
+    for (int T = 0; T < NT; ++T) {
+        acc[T].x = act_apply(acc[T].x, act);
+        acc[T].y = act_apply(acc[T].y, act);
+        acc[T].z = act_apply(acc[T].z, act);
+        acc[T].w = act_apply(acc[T].w, act);
     }
 }
 
@@ -235,10 +254,13 @@ __device__ __forceinline__ void dump_pre(const f32x4 (&acc)[NT], float* base, lo
 // PAD: EVERY layer's real width a.real[l] may be below its tile width (widths between the template grid's: weights,
 // biases and LayerNorm parameters zero padded, W[l >= 1] also in its columns); statistics are masked, dumps, skip
 // and stores use the real row strides.  False for every kernel of the native grid: their code does not depend on it.
+// PLAIN: no layer has a LayerNorm (make_mlp with layer_norm=False): each layer is act(x W^T + b), the activation code
+// read from the descriptor; PARTIAL is then only the store mask of a narrow last layer.  False everywhere else.
 template <int NT1, int NT2, int NT3, int MINW, int ACT_H, int ACT_O, bool PLAIN_LAST = false, int NW = 4,
-          bool PARTIAL = false, bool PAD = false>
+          bool PARTIAL = false, bool PAD = false, bool PLAIN = false>
 __global__ __launch_bounds__(NW * 64, MINW) void k_fused_mlp(const MlpArgs a) {
     static_assert(!PAD || (NT2 > 0 && PARTIAL == PLAIN_LAST), "PAD: 2 or 3 layers; heads keep the PARTIAL store");
+    static_assert(!PLAIN || (NT2 > 0 && !PAD && ACT_H < 0), "PLAIN: 2 or 3 layers of the native grid, runtime codes");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -360,7 +382,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_fused_mlp(const MlpArgs a) {
         store_out<NT1, PARTIAL>(acc1, a, e, valid, g);
         return;
     }
-    if (!(a.ablate & 1))
+    if constexpr (PLAIN) {
+        act_only<NT1>(acc1, a.act[0]);
+    } else if (!(a.ablate & 1))
         layernorm_act<NT1, ACT_H, true, false, PAD>(acc1, a.lnw[0], a.lnb[0], a.act[0], a.eps, g,
                                                     PAD ? a.real[0] : NT1 * 16);
     __builtin_amdgcn_s_setprio(2);
@@ -372,7 +396,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_fused_mlp(const MlpArgs a) {
     dense_from_regs<NT1, N2, NW>(acc1, acc2, a.W[1], lds, wave, lane, a.ablate);
     __builtin_amdgcn_s_setprio(0);
     dump_pre<N2, PAD>(acc2, a.save_pre[1], e, valid, g, PAD ? a.real[1] : N2 * 16);
-    if (!(a.ablate & 1))
+    if constexpr (PLAIN) {
+        act_only<N2>(acc2, a.act[1]);
+    } else if (!(a.ablate & 1))
         layernorm_act<N2, (NT3 == 0 ? ACT_O : ACT_H), !(PLAIN_LAST && NT3 == 0), (PARTIAL && NT3 == 0 && !PAD), PAD>(
             acc2, a.lnw[1], a.lnb[1], a.act[1], a.eps, g, PAD ? a.real[1] : (NT3 == 0 ? a.n_out_real : N2 * 16));
     if constexpr (NT3 == 0) {
@@ -385,7 +411,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_fused_mlp(const MlpArgs a) {
         dense_from_regs<N2, NT3, NW>(acc2, acc3, a.W[2], lds, wave, lane, a.ablate);
         __builtin_amdgcn_s_setprio(0);
         dump_pre<NT3, PAD>(acc3, a.save_pre[2], e, valid, g, PAD ? a.real[2] : NT3 * 16);
-        if (!(a.ablate & 1))
+        if constexpr (PLAIN) {
+            if constexpr (!PLAIN_LAST) act_only<NT3>(acc3, a.act[2]);
+        } else if (!(a.ablate & 1))
             layernorm_act<NT3, ACT_O, !PLAIN_LAST, (PARTIAL && !PAD), PAD>(acc3, a.lnw[2], a.lnb[2], a.act[2], a.eps, g,
                                                                            a.n_out_real);
         if constexpr (PAD && !PLAIN_LAST) store_out_pad<NT3>(acc3, a, e, valid, g);
@@ -394,12 +422,12 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_fused_mlp(const MlpArgs a) {
 }
 
 template <int NT1, int NT2, int NT3, int MINW, int ACT_H, int ACT_O, bool PLAIN_LAST = false, int NW = 4,
-          bool PARTIAL = false, bool PAD = false>
+          bool PARTIAL = false, bool PAD = false, bool PLAIN = false>
 static int launch_mlp_act(const MlpArgs& a, hipStream_t s) {
     constexpr int maxnt = NT1 > NT2 ? (NT1 > NT3 ? NT1 : NT3) : (NT2 > NT3 ? NT2 : NT3);
     const size_t lds_bytes = (size_t)2 * maxnt * 256 * sizeof(float);
     const unsigned grid = (unsigned)ceil_div(a.M, NW * 16);
-    auto kern = k_fused_mlp<NT1, NT2, NT3, MINW, ACT_H, ACT_O, PLAIN_LAST, NW, PARTIAL, PAD>;
+    auto kern = k_fused_mlp<NT1, NT2, NT3, MINW, ACT_H, ACT_O, PLAIN_LAST, NW, PARTIAL, PAD, PLAIN>;
     if (lds_bytes > 64 * 1024) {
         HGNN_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)lds_bytes));
@@ -426,10 +454,16 @@ static int launch_mlp(const MlpArgs& a, hipStream_t s) {
     bool hidden_gelu = true;
     for (int l = 0; l + 1 < n; ++l) hidden_gelu = hidden_gelu && a.act[l] == HGNN_ACT_GELU;
     const int out = a.act[n - 1];
+    if (g_opt_mlp_act_switch) return launch_mlp_act<NT1, NT2, NT3, MINW, -1, -1>(a, s);
     // (round-2 null result, removed: 8 waves = 128 rows per workgroup, one workgroup per CU -- bitwise equal,
     // 3.6 % slower: one phase-locked workgroup does not overlap its epilogue with another's MFMAs)
     if (hidden_gelu && out == HGNN_ACT_TANH) return launch_mlp_act<NT1, NT2, NT3, MINW, HGNN_ACT_GELU, HGNN_ACT_TANH>(a, s);
     if (hidden_gelu && out == HGNN_ACT_GELU) return launch_mlp_act<NT1, NT2, NT3, MINW, HGNN_ACT_GELU, HGNN_ACT_GELU>(a, s);
+    // SiLU in GELU's place (hidden_activation: SiLU): the cell networks' two combinations, compile-time as well
+    bool hidden_silu = true;
+    for (int l = 0; l + 1 < n; ++l) hidden_silu = hidden_silu && a.act[l] == HGNN_ACT_SILU;
+    if (hidden_silu && out == HGNN_ACT_TANH) return launch_mlp_act<NT1, NT2, NT3, MINW, HGNN_ACT_SILU, HGNN_ACT_TANH>(a, s);
+    if (hidden_silu && out == HGNN_ACT_SILU) return launch_mlp_act<NT1, NT2, NT3, MINW, HGNN_ACT_SILU, HGNN_ACT_SILU>(a, s);
     return launch_mlp_act<NT1, NT2, NT3, MINW, -1, -1>(a, s);
 }
 
@@ -604,6 +638,101 @@ extern "C" int hgnn_mlp_forward_f32(const hgnn_mlp_desc* d, float* out, hgnn_str
         }
     }
     set_error("hgnn_mlp_forward_f32: no instantiation");
+    return HGNN_ERR_UNSUPPORTED;
+}
+
+// LayerNorm-less networks (make_mlp with layer_norm=False): the PLAIN kernels, activation codes read per layer
+static bool plain_is_head(const hgnn_mlp_desc* d) {
+    return d->n_layers == 3 && d->w_last_rows == 32 && d->width[3] <= 32 && d->act[2] == HGNN_ACT_NONE;
+}
+
+extern "C" int hgnn_mlp_supported_f32_plain(const hgnn_mlp_desc* d) {
+    if (!mlp_desc_shape_ok(d, kRulesF32Padded)) return 0;   // 2 or 3 layers; segments, w0_cols, n_pre as for the grid kernels
+    const int n = d->n_layers;
+    const int h = d->width[1];
+    const int o = d->width[n];
+    for (int l = 0; l < n; ++l) {
+        if (d->ln_w[l] != nullptr || d->ln_b[l] != nullptr) return 0;   // a mixed network is not this entry's
+        if (d->act[l] < HGNN_ACT_NONE || d->act[l] > HGNN_ACT_LAST) return 0;
+    }
+    if (plain_is_head(d)) {
+        // K -> H -> H -> w (w <= 32): the last layer a plain Linear stored as 32 rows
+        if (o < 1 || d->skip != nullptr || d->save_pre[2] != nullptr) return 0;
+        return (h == 64 || h == 128 || h == 256 || h == 512) ? 1 : 0;
+    }
+    if (d->w_last_rows != 0 && d->w_last_rows != o) {
+        // K -> 2P -> 2P -> o with P - 16 < o < P real outputs, W / b of the last layer zero padded to P rows: without
+        // statistics w_last_rows is only the store mask
+        const int P = d->w_last_rows;
+        if (n != 3 || o < 4 || o <= P - 16 || o >= P || (o & 3) != 0 || h != 2 * P || d->skip != nullptr) return 0;
+        for (int l = 0; l < n; ++l)
+            if (d->save_pre[l] != nullptr) return 0;
+        return (P == 32 || P == 64 || P == 128 || P == 256) ? 1 : 0;
+    }
+    if (h != 2 * o) return 0;
+    return (o == 32 || o == 64 || o == 128 || o == 256) ? 1 : 0;
+}
+
+template <int NT1, int NT2, int NT3, int MINW, bool PLAIN_LAST = false, bool PARTIAL = false>
+static int launch_mlp_plain(const MlpArgs& a, hipStream_t s) {
+    return launch_mlp_act<NT1, NT2, NT3, MINW, -1, -1, PLAIN_LAST, 4, PARTIAL, false, true>(a, s);
+}
+
+extern "C" int hgnn_mlp_forward_f32_plain(const hgnn_mlp_desc* d, float* out, hgnn_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    HGNN_REQUIRE(d != nullptr && out != nullptr, "hgnn_mlp_forward_f32_plain: NULL argument");
+    if (!hgnn_mlp_supported_f32_plain(d)) {
+        set_error("hgnn_mlp_forward_f32_plain: unsupported shape (see hgnn_mlp_supported_f32_plain in "
+                  "include/hgnn_hip.h: K -> 2L (-> 2L) -> L without LayerNorm on any layer, L in {32,64,128,256}, "
+                  "segments multiples of 16 or K <= 16 zero-padded; or a K -> H -> H -> w head)");
+        return HGNN_ERR_UNSUPPORTED;
+    }
+    if (d->M == 0) return HGNN_OK;
+    static const char fn[] = "hgnn_mlp_forward_f32_plain";
+    HGNN_REQUIRE(d->M > 0 && d->M < ((int64_t)1 << 31) * 64, "%s: bad M", fn);
+    const int n = d->n_layers;
+    MlpArgs a;
+    HGNN_TRY(unpack_segments(a, d, fn));
+    a.K1_real = d->width[0];
+    a.n_out_real = d->width[n];
+    for (int l = 0; l < 3; ++l) {
+        HGNN_TRY(unpack_layer(a, d, l, fn));
+        a.real[l] = 0;
+        HGNN_TRY(unpack_save_pre(a, d, l, fn));
+    }
+    a.ablate = 0;
+    HGNN_TRY(unpack_pre(a, d, fn));
+    HGNN_TRY(unpack_out_skip(a, d, out, fn));
+    if (plain_is_head(d)) {
+        switch (d->width[1]) {
+            case 64: return launch_mlp_plain<4, 4, 2, 2, true, true>(a, stream);
+            case 128: return launch_mlp_plain<8, 8, 2, 2, true, true>(a, stream);
+            case 256: return launch_mlp_plain<16, 16, 2, 2, true, true>(a, stream);
+            case 512: return launch_mlp_plain<32, 32, 2, 1, true, true>(a, stream);
+        }
+    } else if (d->w_last_rows != 0 && d->w_last_rows != d->width[n]) {
+        switch (d->w_last_rows) {
+            case 32: return launch_mlp_plain<4, 4, 2, 2, false, true>(a, stream);
+            case 64: return launch_mlp_plain<8, 8, 4, 2, false, true>(a, stream);
+            case 128: return launch_mlp_plain<16, 16, 8, 2, false, true>(a, stream);
+            case 256: return launch_mlp_plain<32, 32, 16, 1, false, true>(a, stream);
+        }
+    } else if (n == 2) {
+        switch (d->width[n]) {
+            case 32: return launch_mlp_plain<4, 2, 0, 2>(a, stream);
+            case 64: return launch_mlp_plain<8, 4, 0, 2>(a, stream);
+            case 128: return launch_mlp_plain<16, 8, 0, 2>(a, stream);
+            case 256: return launch_mlp_plain<32, 16, 0, 2>(a, stream);
+        }
+    } else {
+        switch (d->width[n]) {
+            case 32: return launch_mlp_plain<4, 4, 2, 2>(a, stream);
+            case 64: return launch_mlp_plain<8, 8, 4, 2>(a, stream);
+            case 128: return launch_mlp_plain<16, 16, 8, 2>(a, stream);
+            case 256: return launch_mlp_plain<32, 32, 16, 1>(a, stream);
+        }
+    }
+    set_error("hgnn_mlp_forward_f32_plain: no instantiation");
     return HGNN_ERR_UNSUPPORTED;
 }
 

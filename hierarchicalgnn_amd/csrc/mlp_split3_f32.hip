@@ -857,16 +857,21 @@ static int launch_act(const ArgsOf<PAD>& a, hipStream_t s) {
 // anything else runs the runtime-switch instantiation
 template <int NW, int NTH, int NTO, int NL, bool PAD = false>
 static int launch(const ArgsOf<PAD>& a, hipStream_t s) {
-    bool hidden_gelu = true, hidden_tanh = true;
+    bool hidden_gelu = true, hidden_tanh = true, hidden_silu = true;
     for (int l = 0; l + 1 < NL; ++l) {
         hidden_gelu = hidden_gelu && a.act[l] == HGNN_ACT_GELU;
         hidden_tanh = hidden_tanh && a.act[l] == HGNN_ACT_TANH;
+        hidden_silu = hidden_silu && a.act[l] == HGNN_ACT_SILU;
     }
     const int out = a.act[NL - 1];
+    if (g_opt_mlp_act_switch) return launch_act<NW, NTH, NTO, NL, -1, -1, PAD>(a, s);   // measurement: see mlp_fused.hip
     if (hidden_gelu && out == HGNN_ACT_TANH) return launch_act<NW, NTH, NTO, NL, HGNN_ACT_GELU, HGNN_ACT_TANH, PAD>(a, s);
     if (hidden_gelu && out == HGNN_ACT_GELU) return launch_act<NW, NTH, NTO, NL, HGNN_ACT_GELU, HGNN_ACT_GELU, PAD>(a, s);
     if constexpr (!PAD) {   // (score heads: no PAD shape)
         if (hidden_tanh && out == HGNN_ACT_TANH) return launch_act<NW, NTH, NTO, NL, HGNN_ACT_TANH, HGNN_ACT_TANH>(a, s);
+        // SiLU in GELU's place: the cell networks' two combinations (the padded widths keep the runtime switch)
+        if (hidden_silu && out == HGNN_ACT_TANH) return launch_act<NW, NTH, NTO, NL, HGNN_ACT_SILU, HGNN_ACT_TANH>(a, s);
+        if (hidden_silu && out == HGNN_ACT_SILU) return launch_act<NW, NTH, NTO, NL, HGNN_ACT_SILU, HGNN_ACT_SILU>(a, s);
     }
     return launch_act<NW, NTH, NTO, NL, -1, -1, PAD>(a, s);
 }

@@ -528,8 +528,11 @@ static int launch_tile_act(const Args& a, hipStream_t s) {
 }
 
 static int launch_tile(const Args& a, hipStream_t s) {
+    if (g_opt_mlp_act_switch) return launch_tile_act<-1, -1>(a, s);   // measurement: see mlp_fused.hip
     if (a.act[0] == HGNN_ACT_GELU && a.act[1] == HGNN_ACT_TANH) return launch_tile_act<HGNN_ACT_GELU, HGNN_ACT_TANH>(a, s);
     if (a.act[0] == HGNN_ACT_GELU && a.act[1] == HGNN_ACT_GELU) return launch_tile_act<HGNN_ACT_GELU, HGNN_ACT_GELU>(a, s);
+    if (a.act[0] == HGNN_ACT_SILU && a.act[1] == HGNN_ACT_TANH) return launch_tile_act<HGNN_ACT_SILU, HGNN_ACT_TANH>(a, s);
+    if (a.act[0] == HGNN_ACT_SILU && a.act[1] == HGNN_ACT_SILU) return launch_tile_act<HGNN_ACT_SILU, HGNN_ACT_SILU>(a, s);
     return launch_tile_act<-1, -1>(a, s);
 }
 }  // namespace HGNN_KH_NS

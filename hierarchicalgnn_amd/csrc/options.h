@@ -13,6 +13,7 @@ extern int g_opt_k1_window;  // segreduce.hip
 extern int g_opt_k1_waves;   // segreduce.hip
 #endif
 extern int g_opt_mlp_ablate;         // mlp_fused.hip; read by the bf16 MLPs too
+extern int g_opt_mlp_act_switch;     // mlp_fused.hip; read by the split-bf16 fp32 MLP too
 extern int g_opt_mlp_split_variant;  // mlp_split_bf16.hip
 namespace f3 {
 extern int g_opt_split3_rows128;  // mlp_split3_f32.hip

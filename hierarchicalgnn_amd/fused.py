@@ -3,6 +3,8 @@
 (csrc/mlp_fused_bf16.hip, bf16 rows).  Covers the cell networks, the encoders (small-K mode)
 and the width-1 classifier heads; fp32 rows at every hidden width that is a multiple of 16 up to 512
 (``hgnn_mlp_forward_f32_padded``: zero-padded parameters on the next instantiation of the template grid).
+Activations: GELU, Tanh, ReLU, SiLU, LeakyReLU, ELU, Sigmoid at their constructor defaults (``_ACT``).  Networks without
+LayerNorm (``layer_norm=False``): opt-in route ``f32_plain`` (``set_plain_layers``, ``hgnn_mlp_forward_f32_plain``).
 
 ``_route`` decides per call (``supported`` asks it); when it says no, ``concat_mlp`` evaluates the same
 Sequential with HIP row gathers + library GEMMs (still on the GPU).  The fused kernel is
@@ -29,7 +31,8 @@ import torch.nn as nn
 from . import _lib
 from .plan import get_index32
 
-_ACT = {nn.GELU: 1, nn.Tanh: 2, nn.ReLU: 3}
+# HGNN_ACT_* (include/hgnn_hip.h).  4..7 at their constructor defaults only (``_act_code``)
+_ACT = {nn.GELU: 1, nn.Tanh: 2, nn.ReLU: 3, nn.SiLU: 4, nn.LeakyReLU: 5, nn.ELU: 6, nn.Sigmoid: 7}
 _enabled = True
 # The differentiable variant (kernel forward + hand-written backward).  With ATen elementwise kernels in
 # the backward it was 2 % slower than autograd through the library path; with the one-pass HIP
@@ -46,8 +49,9 @@ _train_enabled = True
 # narrow_outer_calls / library_head_calls, a head's plain last Linear (``set_project_f32``, ``set_narrow_f32``).  While
 # ``set_narrow_f32`` is on, library_dgrad_calls also counts a first-layer input gradient of the fp32 backward that stays
 # on the library
+# plain_calls: launches of hgnn_mlp_forward_f32_plain (``set_plain_layers``), no-grad and differentiable
 stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0, "library_calls": 0, "library_dgrad_calls": 0,
-         "bwd_layer_calls": 0, "hybrid_train_calls": 0, "bwd_layer_f32_calls": 0}
+         "bwd_layer_calls": 0, "hybrid_train_calls": 0, "bwd_layer_f32_calls": 0, "plain_calls": 0}
 
 # Dispatch switches.  The module-level ``_name`` variables below are the PROCESS DEFAULTS (what the ``set_*`` functions
 # and the HGNN_* environment variables change).  ``options(...)`` overrides any of them for the current context only --
@@ -56,7 +60,7 @@ stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0, "library_c
 _ctx_options = contextvars.ContextVar("hgnn_fused_options", default=None)
 _ctx_training_forward = contextvars.ContextVar("hgnn_fused_training_forward", default=0)
 _OPTION_NAMES = ("enabled", "train_enabled", "preproject", "preproject_bf16", "fp32_split3", "fp32_split3_train",
-                 "bf16_split", "train_bf16_enabled", "strict", "split3_padded")
+                 "bf16_split", "train_bf16_enabled", "strict", "split3_padded", "plain_layers")
 
 
 def _opt(name: str):
@@ -69,7 +73,8 @@ def _opt(name: str):
 @contextlib.contextmanager
 def options(**overrides):
     """Context-local dispatch overrides: ``enabled``, ``train_enabled``, ``preproject``, ``preproject_bf16``,
-    ``fp32_split3``, ``fp32_split3_train``, ``bf16_split``, ``train_bf16_enabled``, ``strict``, ``split3_padded``.
+    ``fp32_split3``, ``fp32_split3_train``, ``bf16_split``, ``train_bf16_enabled``, ``strict``, ``split3_padded``,
+    ``plain_layers`` (see ``set_plain_layers``).
     ``strict``: ``concat_mlp`` raises instead of evaluating a Sequential on the library path (see ``set_strict``).
     Nested contexts stack; nothing outside the ``with`` block (or in another thread) sees the change.
     NOTE for training: autograd runs the backward (and the recompute of reentrant checkpoints) on its own worker
@@ -109,12 +114,27 @@ def set_strict(flag: bool) -> None:
     _strict = bool(flag)
 
 
+def _act_code(act) -> int:
+    """HGNN_ACT_* of an activation module at the parameters the kernels implement (the constructor defaults:
+    erf GELU, LeakyReLU slope 0.01, ELU alpha 1.0), or 0"""
+    code = _ACT.get(type(act), 0)
+    if isinstance(act, nn.GELU) and getattr(act, "approximate", "none") != "none":
+        return 0
+    if isinstance(act, nn.LeakyReLU) and act.negative_slope != 0.01:
+        return 0
+    if isinstance(act, nn.ELU) and act.alpha != 1.0:
+        return 0
+    return code
+
+
 def _parse(net: nn.Sequential):
-    """[(Linear, LayerNorm or None, act_code)] or None if the Sequential is not
-    (Linear -> LayerNorm -> act) repeated, optionally ending in one plain Linear (a head)"""
+    """[(Linear, LayerNorm or None, act_code)] or None if the Sequential is neither
+    (Linear -> LayerNorm -> act) repeated nor -- the plain form, make_mlp with layer_norm=False -- (Linear -> act)
+    repeated, either optionally ending in one plain Linear (a head).  A network that mixes the two is None"""
     mods = list(net)
     layers = []
     i = 0
+    plain = len(mods) > 1 and not isinstance(mods[1], (nn.LayerNorm, nn.Linear))
     while i < len(mods):
         lin = mods[i]
         if not isinstance(lin, nn.Linear) or lin.bias is None:
@@ -122,18 +142,28 @@ def _parse(net: nn.Sequential):
         if i + 1 == len(mods):                       # plain last layer (output_activation=None)
             layers.append((lin, None, 0))
             break
+        if plain:
+            code = _act_code(mods[i + 1])
+            if not code:
+                return None
+            layers.append((lin, None, code))
+            i += 2
+            continue
         if i + 2 >= len(mods):
             return None
         ln, act = mods[i + 1], mods[i + 2]
-        if not isinstance(ln, nn.LayerNorm) or type(act) not in _ACT:
-            return None
-        if isinstance(act, nn.GELU) and getattr(act, "approximate", "none") != "none":
+        if not isinstance(ln, nn.LayerNorm) or not _act_code(act):
             return None
         if not ln.elementwise_affine or ln.bias is None:
             return None
         layers.append((lin, ln, _ACT[type(act)]))
         i += 3
     return layers or None
+
+
+def _is_plain(layers) -> bool:
+    """``_parse``'s plain form: at least one activated layer, no LayerNorm anywhere"""
+    return layers is not None and layers[0][2] != 0 and all(ln is None for _, ln, _ in layers)
 
 
 _preproject = True
@@ -223,18 +253,22 @@ def _layout_f32(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
         # parameters zero-padded to 512 rows, statistics and stores over the real width
         rows = 512
 
-    def make():
-        if not (cols or small_k or rows):
-            return raw
-        W = raw[0].detach()
-        if cols:
-            W = torch.cat([W[:, c0:c1] for c0, c1 in cols], dim=1).contiguous()
-        if small_k:
-            # small-K mode (encoders, K = 3 / 6): one zero-padded 16-column chunk
-            W = torch.nn.functional.pad(W, (0, 16 - K)).contiguous()
-        ps = (W,) + raw[1:]
-        return ps if not rows else [p if p is None else _pad_rows(p.detach(), rows) for p in ps]
-    return 16 if small_k else 0, rows, make
+    return 16 if small_k else 0, rows, lambda: _f32_params(raw, cols, K, small_k, rows)
+
+
+def _f32_params(raw, cols, K, small_k, rows):
+    """the (W, b, ln_w, ln_b) the exact fp32 kernel reads (``_layout_f32``, ``_layout_f32_plain``): the kept column
+    blocks of the first layer, small-K padding, a last layer zero padded to ``rows`` rows"""
+    if not (cols or small_k or rows):
+        return raw
+    W = raw[0].detach()
+    if cols:
+        W = torch.cat([W[:, c0:c1] for c0, c1 in cols], dim=1).contiguous()
+    if small_k:
+        # small-K mode (encoders, K = 3 / 6): one zero-padded 16-column chunk
+        W = torch.nn.functional.pad(W, (0, 16 - K)).contiguous()
+    ps = (W,) + raw[1:]
+    return ps if not rows else [p if p is None else _pad_rows(p.detach(), rows) for p in ps]
 
 
 def _layout_f32_padded(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
@@ -291,7 +325,23 @@ def _layout_f32_split3_padded(l, n, lin, ln, raw, cols, K, small_k, hidden, P_gr
     return 0, rows if last else 0, make
 
 
-_LAYOUTS = {"f32": _layout_f32, "f32_padded": _layout_f32_padded, "f32_split3": _layout_f32_split3,
+def _layout_f32_plain(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
+    """no LayerNorm on any layer (hgnn_mlp_forward_f32_plain): ``_layout_f32``'s storage -- a head's last Linear as 32
+    rows, the narrow encoder's as hidden / 2 rows (here only a store mask)"""
+    if ln is not None:
+        return None
+    o, last, rows = int(lin.out_features), l == n - 1, 0
+    if last and n == 3 and hidden != 2 * o:
+        if o <= 32:
+            rows = 32
+        elif hidden % 2 == 0 and hidden // 2 - 16 < o < hidden // 2 and o % 4 == 0:
+            rows = hidden // 2
+        else:
+            return None
+    return 16 if small_k else 0, rows, lambda: _f32_params(raw, cols, K, small_k, rows)
+
+
+_LAYOUTS = {"f32": _layout_f32, "f32_plain": _layout_f32_plain, "f32_padded": _layout_f32_padded, "f32_split3": _layout_f32_split3,
             "f32_split3_padded": _layout_f32_split3_padded, "bf16": _layout_bf16, "bf16_split": _layout_bf16_split}
 
 
@@ -349,7 +399,7 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
     layers = _parse(net) if layers is None else layers
     if layers is None or not (1 <= len(layers) <= 3 and 1 <= len(segments) <= 3):
         return None
-    if any(ln is None for _, ln, _ in (layers if bf16 else layers[:-1])) \
+    if (entry != "f32_plain" and any(ln is None for _, ln, _ in (layers if bf16 else layers[:-1]))) \
             or any(t.dim() != 2 or not t.is_cuda or t.dtype != dt for t, _ in segments):
         return None
     M, *more = {int(i.numel()) if i is not None else int(t.shape[0]) for t, i in segments}
@@ -366,7 +416,7 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
         pre = _opt("preproject_bf16")
         pre = entry == "bf16_split" and (len(layers) > 1 and hidden >= 512 if pre is None else pre)
     else:
-        pre = layers[0][1] is not None
+        pre = layers[0][1] is not None or entry == "f32_plain"
     proj = _projected_segments(segments, M) if pre else []
     tables = [t if t.is_contiguous() else t.contiguous() for t, _ in segments]
     cols = [(sum(ws[:i]), sum(ws[:i + 1])) for i in range(len(ws))]
@@ -426,7 +476,7 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
                 return None
         o_l = d.width[l + 1] = int(lin.out_features)
         d.act[l] = act
-    d.ln_eps = float(eps)
+    d.ln_eps = float(eps) if eps is not None else 0.0     # f32_plain: not read
     n_out = int(d.width[n])
     if skip is not None:
         if tuple(skip.shape) != (M, n_out) or not skip.is_cuda or skip.dtype != dt:
@@ -639,6 +689,27 @@ def _split3_padded_weight(weight, rows: int, cols: Optional[int], kept_cols):
     return _cached(weight, ("split3_padded", rows, cols, kept_cols), make)
 
 
+_plain_layers = os.environ.get("HGNN_MLP_PLAIN", "0") == "1"
+
+
+def set_plain_layers(flag: bool) -> None:
+    """OPT-IN (HGNN_MLP_PLAIN=1, ``options(plain_layers=True)``): fp32 networks WITHOUT LayerNorm (make_mlp with
+    layer_norm=False, ``layernorm: False`` in a config) run on the exact fp32 kernel's plain form
+    (hgnn_mlp_forward_f32_plain: each layer act(x W^T + b)) at the shapes the LayerNorm'ed networks have there -- cell
+    networks and encoders at latent 32 / 64 / 128 / 256, the K -> H -> H -> w heads, the narrow supernode encoder.
+    Under autograd the same kernel dumps the pre-activation rows and the backward uses hgnn_act_rows_backward_f32 and
+    the GEMMs of the LayerNorm'ed path (``set_wgrad_f32`` / ``set_narrow_f32`` apply; ``set_bwd_layer_f32`` does not:
+    the fused backward layer has no plain form).  bf16 rows, the padded widths, latent 512 and the split-bf16
+    arithmetic have no plain form and keep the library path.  A backward and the recompute of a reentrant checkpoint run
+    on autograd's own thread, which only the process default set here reaches.  Default off."""
+    global _plain_layers
+    _plain_layers = bool(flag)
+
+
+def _plain_layers_on() -> bool:
+    return bool(_opt("plain_layers"))
+
+
 _split3_padded = os.environ.get("HGNN_SPLIT3_PADDED", "0") == "1"
 
 
@@ -787,6 +858,22 @@ def _route(net, segments, skip, *, train: bool, allow_chain: bool = True) -> Opt
         return None
     lib = _lib.load()
     bf16 = _is_bf16(segments)
+    if _is_plain(layers):
+        # no LayerNorm anywhere (layernorm: False): opt-in, fp32 rows, the exact kernel's plain form -- inference and
+        # training alike; everything else (bf16 rows, shapes off its grid) is the library path's
+        if not _plain_layers_on() or bf16 or len(layers) < 2:
+            return None
+        try:
+            desc = _descriptor(net, segments, skip, "f32_plain", dry=True, layers=layers)
+        except RuntimeError:
+            return None
+        if desc is None or not lib.hgnn_mlp_supported_f32_plain(ctypes.byref(desc[0])):
+            return None
+        if train and int(desc[0].w_last_rows) != 0 and not (layers[-1][2] == 0 and layers[-1][0].out_features <= 32):
+            # a last layer narrower than its storage that is no head (the supernode encoder): its dumps are refused by
+            # the entry, so it trains on the library path (counted in library_calls)
+            return None
+        return _Route(net, layers, "f32_plain", train=train)
 
     def dry(entry, lays=layers, sk=skip):
         """(dry descriptor or None, whether the kernel's own check accepts it)"""
@@ -909,6 +996,8 @@ def _forward(entry, d, out, dev):
         stats["padded_calls"] += 1
     elif entry == "f32_split3_padded":
         stats["split3_padded_calls"] = stats.get("split3_padded_calls", 0) + 1
+    elif entry == "f32_plain":
+        stats["plain_calls"] += 1
 
 
 def _launch(layers, segments, skip, entry, split_proj=False, out=None):
@@ -933,6 +1022,10 @@ def _run(r: _Route, segments, skip, out=None):
     tensor (no-grad callers that assemble one edge table from several calls -- the interior / boundary split of a sharded
     edge update -- avoid a 2 GB concatenation); only the single-launch paths write into it directly"""
     layers = r.layers
+    if r.train and r.entry == "f32_plain":
+        tables, indices = [t for t, _ in segments], tuple(i for _, i in segments)
+        params = [p for lin, _, _ in layers for p in (lin.weight, lin.bias)]
+        return _PlainMLPTrain.apply(r, indices, skip is not None, *tables, *([skip] if skip is not None else []), *params)
     if r.train:
         tables, indices = [t for t, _ in segments], tuple(i for _, i in segments)
         params = []
@@ -1060,6 +1153,24 @@ def _atb(A: torch.Tensor, B: torch.Tensor, net=None) -> torch.Tensor:
     return out
 
 
+_ATEN_ACT = {1: torch.nn.functional.gelu, 2: torch.tanh, 3: torch.relu, 4: torch.nn.functional.silu,
+             5: torch.nn.functional.leaky_relu, 6: torch.nn.functional.elu, 7: torch.sigmoid}
+
+
+def _aten_act(y, code: int):
+    """act(y) with ATen kernels: rows of a width the HIP row kernels have no instantiation for"""
+    return _ATEN_ACT[code](y) if code else y
+
+
+def _aten_act_backward(da, y, code: int):
+    """da * act'(y) through ATen's own derivative of the activation (same widths as ``_aten_act``)"""
+    if not code:
+        return da
+    with torch.enable_grad():
+        yy = y.detach().requires_grad_(True)
+        return torch.autograd.grad(_ATEN_ACT[code](yy), yy, da)[0]
+
+
 def _zero_grads(ctx, tables, params, grad_out, n_seg):
     """backward of an MLP that was called on M == 0 rows (a shard without edges, an empty super graph): every
     parameter and table gradient is zero; no kernel is launched"""
@@ -1178,8 +1289,7 @@ class _FusedMLPTrain(torch.autograd.Function):
                 rstds.append(rstd)
                 code = ctx.acts[l]
                 if l < n - 1 or code == 2:
-                    outs.append(torch.tanh(y) if code == 2 else (torch.nn.functional.gelu(y) if code == 1
-                                else (torch.relu(y) if code == 3 else y)))
+                    outs.append(_aten_act(y, code))
                 else:
                     outs.append(None)
         grads_params = [None] * (4 * n)
@@ -1204,6 +1314,8 @@ class _FusedMLPTrain(torch.autograd.Function):
                     dy = aten.tanh_backward(da, outs[l])
                 elif code == 3:
                     dy = da * (ys[l] > 0)
+                elif code >= 4:
+                    dy = _aten_act_backward(da, ys[l], code)
                 else:
                     dy = da
                 dz, dlw, dlb = aten.native_layer_norm_backward(dy, zs[l], [zs[l].shape[1]], means[l], rstds[l],
@@ -1279,6 +1391,129 @@ def fused_concat_mlp_train(net, segments, skip: Optional[torch.Tensor]):
     if r is None:
         raise RuntimeError("fused_concat_mlp_train: unsupported arguments (call supported_train() first)")
     return _run(r, segments, skip)
+
+
+# --------------------------------------------------------------------------- LayerNorm-less training variant
+_ROW_WIDTHS = (64, 128, 256, 512, 1024)
+
+
+def _act_rows_forward(z, act: int):
+    """act(z) in one HIP pass (hgnn_act_rows_forward_f32); ATen at a width without instantiation"""
+    M, W = int(z.shape[0]), int(z.shape[1])
+    if W not in _ROW_WIDTHS or z.dtype != torch.float32:
+        return _aten_act(z, act)
+    out = torch.empty_like(z)
+    if M:
+        zc = _aligned16(z.contiguous())
+        with torch.cuda.device(z.device):
+            _lib.check(_lib.load().hgnn_act_rows_forward_f32(_lib.ptr(zc), M, W, int(act), _lib.ptr(out),
+                                                             _lib.current_stream(z.device)), "hgnn_act_rows_forward_f32")
+    return out
+
+
+def _act_rows_backward(z, grad_out, act: int):
+    """(grad_z, grad_bias) of a = act(z), z = x W^T + bias, in one HIP pass (hgnn_act_rows_backward_f32)"""
+    M, W = int(z.shape[0]), int(z.shape[1])
+    if W not in _ROW_WIDTHS or z.dtype != torch.float32:
+        dz = _aten_act_backward(grad_out, z, act)
+        return dz, dz.sum(dim=0)
+    dz = torch.empty_like(z)
+    partials = torch.empty((_lib.LN_ACT_BLOCKS, W), dtype=torch.float32, device=z.device)
+    go = _aligned16(grad_out.contiguous().to(z.dtype))
+    zc = _aligned16(z.contiguous())
+    with torch.cuda.device(z.device):
+        _lib.check(_lib.load().hgnn_act_rows_backward_f32(_lib.ptr(zc), _lib.ptr(go), M, W, int(act), _lib.ptr(dz),
+                                                          _lib.ptr(partials), _lib.current_stream(z.device)),
+                   "hgnn_act_rows_backward_f32")
+    return dz, partials.sum(dim=0)
+
+
+class _PlainMLPTrain(torch.autograd.Function):
+    """Differentiable fused MLP without LayerNorm (route ``f32_plain``).  Forward: hgnn_mlp_forward_f32_plain dumping
+    each activated layer's pre-activation rows z_l; a last layer without activation (a head's plain Linear) needs no
+    dump, its dz is the incoming gradient.  Backward: dz_l = da_l * act'(z_l) with the bias gradient in one row pass
+    (hgnn_act_rows_backward_f32), hidden activations recomputed from z_l (hgnn_act_rows_forward_f32), weight and data
+    gradients exactly as in ``_FusedMLPTrain`` (``_atb``, gathered segments through the segmented reduce)."""
+
+    @staticmethod
+    def forward(ctx, route, indices, has_skip, *tensors):
+        n_seg = len(indices)
+        tables = list(tensors[:n_seg])
+        skip = tensors[n_seg] if has_skip else None
+        params = tensors[n_seg + (1 if has_skip else 0):]
+        desc = _descriptor(route.net, list(zip(tables, indices)), skip, "f32_plain", layers=route.layers)
+        if desc is None:
+            raise RuntimeError("fused_concat_mlp_train (plain): unsupported arguments (call supported_train() first)")
+        d, keep, M, n_out = desc
+        n, dev = int(d.n_layers), tables[0].device
+        acts = [int(d.act[l]) for l in range(n)]
+        zs = [torch.empty((M, int(d.width[l + 1])), dtype=torch.float32, device=dev)
+              for l in range(n) if l < n - 1 or acts[l] != 0]
+        for l, z in enumerate(zs):
+            d.save_pre[l] = z.data_ptr() if M else None
+        out = torch.empty((M, n_out), dtype=torch.float32, device=dev)
+        if M:
+            with torch.cuda.device(dev):
+                _forward("f32_plain", d, out, dev)
+        del keep
+        stats["fused_train_calls"] += 1
+        ctx.indices, ctx.has_skip, ctx.n, ctx.net, ctx.layers, ctx.acts = indices, has_skip, n, route.net, route.layers, acts
+        ctx.save_for_backward(*tables, *params, *zs)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        with torch.autocast("cuda", enabled=False):
+            return _PlainMLPTrain._backward(ctx, grad_out.float())
+
+    @staticmethod
+    def _backward(ctx, grad_out):
+        from .ops import _seg_reduce
+        from .plan import get_plan
+        n, indices, acts = ctx.n, ctx.indices, ctx.acts
+        n_seg = len(indices)
+        saved = ctx.saved_tensors
+        tables = saved[:n_seg]
+        params = saved[n_seg:n_seg + 2 * n]
+        zs = saved[n_seg + 2 * n:]
+        if int(grad_out.shape[0]) == 0:
+            return _zero_grads(ctx, tables, params, grad_out, n_seg)
+        W = [params[2 * l] for l in range(n)]
+        lw = [lin.weight for lin, _, _ in ctx.layers]
+        g = grad_out.contiguous()
+        grads_params = [None] * (2 * n)
+        grads_tables = [None] * n_seg
+        da = g
+        for l in range(n - 1, -1, -1):
+            if acts[l] != 0:
+                dz, dbias = _act_rows_backward(zs[l], da, acts[l])
+            else:
+                dz, dbias = da, da.sum(dim=0)
+            grads_params[2 * l + 1] = dbias
+            if l > 0:
+                a_prev = _act_rows_forward(zs[l - 1], acts[l - 1])
+                grads_params[2 * l] = _atb(dz, a_prev, ctx.net)
+                del a_prev
+                da = dz @ W[l]
+                continue
+            # first layer: gathered segments factor through S = segment_reduce(dz, idx) (see _FusedMLPTrain)
+            dW_cols = []
+            col = 0
+            for s_i in range(n_seg):
+                idx = indices[s_i]
+                tab = tables[s_i].contiguous()
+                w_s = int(tab.shape[1])
+                W_s = W[0][:, col:col + w_s]
+                src = dz if idx is None else _seg_reduce(get_plan(idx, int(tab.shape[0])), dz, None, None)
+                dW_cols.append(_atb(src, tab, ctx.net))
+                if ctx.needs_input_grad[3 + s_i]:
+                    gt = _narrow_dgrad(src, W_s, lw[0], (col, col + w_s))
+                    grads_tables[s_i] = gt if gt is not None else src @ W_s
+                del src
+                col += w_s
+            grads_params[0] = dW_cols[0] if n_seg == 1 else torch.cat(dW_cols, dim=1)
+        grad_skip = [g] if ctx.has_skip else []
+        return (None, None, None, *grads_tables, *grad_skip, *grads_params)
 
 
 # --------------------------------------------------------------------------- bf16 training variant

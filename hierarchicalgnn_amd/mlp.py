@@ -77,7 +77,8 @@ def concat_mlp(net: nn.Sequential, segments: Sequence[Segment], skip: Optional[t
     if not torch.is_grad_enabled() and fused._opt("enabled") and not bf16_tail \
             and fused._ctx_training_forward.get() == 0 \
             and all(t.dtype == torch.bfloat16 and t.is_cuda for t, _ in segments) \
-            and (skip is None or skip.dtype == torch.bfloat16) and next(net.parameters()).dtype == torch.float32:
+            and (skip is None or skip.dtype == torch.bfloat16) and next(net.parameters()).dtype == torch.float32 \
+            and not fused._is_plain(fused._parse(net)):    # bf16 rows without LayerNorm keep the library path
         # bf16 rows and a net no bf16 kernel accepts (the supernode encoder, latent - emb_dim outputs: the bf16 kernels
         # have no real-width LayerNorm): the fp32 kernels on the rows cast up, the result cast down -- a few thousand
         # pooled rows, the casts are noise.  Not in the no-grad pass of a checkpointed training step: its recompute

@@ -331,6 +331,13 @@ int hgnn_cc_labels(const int64_t* src, const int64_t* dst, int64_t M, int64_t n,
 #define HGNN_ACT_GELU 1 /* erf form, nn.GELU() default */
 #define HGNN_ACT_TANH 2
 #define HGNN_ACT_RELU 3
+/* 4..7: the torch.nn classes make_mlp is given by name, at their constructor defaults (the reference builds them with
+ * no arguments).  Forms and error bounds: csrc/mlp_common.h */
+#define HGNN_ACT_SILU 4       /* x * sigmoid(x), nn.SiLU()                                 */
+#define HGNN_ACT_LEAKY_RELU 5 /* negative_slope = 0.01, nn.LeakyReLU()                     */
+#define HGNN_ACT_ELU 6        /* alpha = 1.0, nn.ELU()                                     */
+#define HGNN_ACT_SIGMOID 7    /* nn.Sigmoid()                                              */
+#define HGNN_ACT_LAST HGNN_ACT_SIGMOID /* the entries refuse a code above this one         */
 
 typedef struct hgnn_mlp_desc {
     int32_t n_seg;               /* 1..3 input segments, concatenated in order    */
@@ -415,6 +422,22 @@ int hgnn_mlp_forward_f32(const hgnn_mlp_desc* d, float* out, hgnn_stream_t strea
  * The check accepts grid shapes too (no padding); hgnn_mlp_supported / hgnn_mlp_forward_f32 do not read this layout. */
 int hgnn_mlp_supported_f32_padded(const hgnn_mlp_desc* d);
 int hgnn_mlp_forward_f32_padded(const hgnn_mlp_desc* d, float* out, hgnn_stream_t stream);
+
+/* Networks WITHOUT LayerNorm (make_mlp with layer_norm=False, the reference's default): the same exact-fp32 kernel
+ * with the statistics left out, each layer act[l](x W^T + b).  Same descriptor; ln_w[l] == ln_b[l] == NULL on EVERY
+ * layer (a network that mixes LayerNorm'ed and plain layers is refused here; hgnn_mlp_supported keeps refusing a plain
+ * hidden layer).  ln_eps is not read.  act[l] in HGNN_ACT_NONE .. HGNN_ACT_LAST.  Shapes: the multi-layer grid shapes of
+ * hgnn_mlp_supported --
+ *   cell networks / encoders: K -> 2L (-> 2L) -> L, L in {32, 64, 128, 256}; segments multiples of 16, or K <= 16 in
+ *       small-K mode (w0_cols = 16); skip, n_pre and save_pre allowed; w_last_rows = 0 (or L);
+ *   heads: K -> H -> H -> w, 1 <= w <= 32, act[2] = HGNN_ACT_NONE, the last W / b stored zero padded as 32 rows
+ *       (w_last_rows = 32), H in {64, 128, 256, 512}, no skip, save_pre[0..1] allowed; out is float[M, w];
+ *   narrow encoders: K -> 2P -> 2P -> o, P in {32, 64, 128, 256}, P - 16 < o < P, o % 4 == 0, the last W / b zero
+ *       padded to P rows (w_last_rows = P: here only a store mask), no skip, no save_pre; out is float[M, o].
+ * save_pre[l] receives layer l's pre-activation rows z_l = x W^T + b.  Single layers, the padded widths and the
+ * split-bf16 / bf16 kernels have no plain form. */
+int hgnn_mlp_supported_f32_plain(const hgnn_mlp_desc* d);
+int hgnn_mlp_forward_f32_plain(const hgnn_mlp_desc* d, float* out, hgnn_stream_t stream);
 
 /* bf16 variant (BASELINE config 4 dtype) on v_mfma_f32_16x16x32_bf16.  Same descriptor, read as:
  * seg_table / skip / out = bf16 rows; W[l] = bf16 [out][in] row-major, and for l >= 1 with its
@@ -511,6 +534,15 @@ int hgnn_ln_act_forward_f32(const float* z, int64_t M, int32_t W, const float* g
 int hgnn_ln_act_backward_f32(const float* z, const float* grad_out, int64_t M, int32_t W, const float* gamma,
                              const float* beta, int32_t act, float eps, float* grad_z,
                              float* partials /* [HGNN_LN_ACT_BLOCKS][3][W] */, hgnn_stream_t stream);
+
+/* The LayerNorm-less twins (a layer of hgnn_mlp_forward_f32_plain; z as dumped by its save_pre), same kernel body,
+ * same widths and alignment rules:
+ *   forward :  out[r]    = act(z[r])
+ *   backward:  grad_z[r] = grad_out[r] * act'(z[r]); partials[b][c] = workgroup b's column sum of grad_z (the
+ *              gradient of the Linear's bias), HGNN_LN_ACT_BLOCKS rows the caller adds (no atomics). */
+int hgnn_act_rows_forward_f32(const float* z, int64_t M, int32_t W, int32_t act, float* out, hgnn_stream_t stream);
+int hgnn_act_rows_backward_f32(const float* z, const float* grad_out, int64_t M, int32_t W, int32_t act,
+                               float* grad_z, float* partials /* [HGNN_LN_ACT_BLOCKS][W] */, hgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * bf16 training path (BASELINE config 4 dtype): backward of the make_mlp Linear layers
