@@ -185,6 +185,8 @@ _SIGNATURES = {
     "hgnn_mlp_forward_f32_padded": (c_int, [POINTER(HgnnMlpDesc), c_void_p, c_void_p]),
     "hgnn_mlp_supported_f32_plain": (c_int, [POINTER(HgnnMlpDesc)]),
     "hgnn_mlp_forward_f32_plain": (c_int, [POINTER(HgnnMlpDesc), c_void_p, c_void_p]),
+    "hgnn_mlp_supported_f32_square": (c_int, [POINTER(HgnnMlpDesc)]),
+    "hgnn_mlp_forward_f32_square": (c_int, [POINTER(HgnnMlpDesc), c_void_p, c_void_p]),
     "hgnn_act_rows_forward_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "hgnn_act_rows_backward_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                                            c_void_p]),

@@ -2,7 +2,9 @@
 ``hgnn_mlp_forward_f32`` (csrc/mlp_fused.hip, fp32 rows) and ``hgnn_mlp_forward_bf16``
 (csrc/mlp_fused_bf16.hip, bf16 rows).  Covers the cell networks, the encoders (small-K mode)
 and the width-1 classifier heads; fp32 rows at every hidden width that is a multiple of 16 up to 512
-(``hgnn_mlp_forward_f32_padded``: zero-padded parameters on the next instantiation of the template grid).
+(``hgnn_mlp_forward_f32_padded``: zero-padded parameters on the next instantiation of the template grid), networks
+whose output is as wide as their hidden layers, single layers below 512 and networks of 4 to 8 layers
+(``hgnn_mlp_forward_f32_square``, csrc/mlp_fused_square.hip; ``set_square``, ``_group_route``).
 Activations: GELU, Tanh, ReLU, SiLU, LeakyReLU, ELU, Sigmoid at their constructor defaults (``_ACT``).  Networks without
 LayerNorm (``layer_norm=False``): opt-in route ``f32_plain`` (``set_plain_layers``, ``hgnn_mlp_forward_f32_plain``).
 
@@ -50,8 +52,9 @@ _train_enabled = True
 # ``set_narrow_f32`` is on, library_dgrad_calls also counts a first-layer input gradient of the fp32 backward that stays
 # on the library
 # plain_calls: launches of hgnn_mlp_forward_f32_plain (``set_plain_layers``), no-grad and differentiable
+# square_calls: launches of hgnn_mlp_forward_f32_square (hidden = output, single layers, the groups of a deep network)
 stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0, "library_calls": 0, "library_dgrad_calls": 0,
-         "bwd_layer_calls": 0, "hybrid_train_calls": 0, "bwd_layer_f32_calls": 0, "plain_calls": 0}
+         "bwd_layer_calls": 0, "hybrid_train_calls": 0, "bwd_layer_f32_calls": 0, "plain_calls": 0, "square_calls": 0}
 
 # Dispatch switches.  The module-level ``_name`` variables below are the PROCESS DEFAULTS (what the ``set_*`` functions
 # and the HGNN_* environment variables change).  ``options(...)`` overrides any of them for the current context only --
@@ -60,7 +63,7 @@ stats = {"fused_calls": 0, "fused_train_calls": 0, "padded_calls": 0, "library_c
 _ctx_options = contextvars.ContextVar("hgnn_fused_options", default=None)
 _ctx_training_forward = contextvars.ContextVar("hgnn_fused_training_forward", default=0)
 _OPTION_NAMES = ("enabled", "train_enabled", "preproject", "preproject_bf16", "fp32_split3", "fp32_split3_train",
-                 "bf16_split", "train_bf16_enabled", "strict", "split3_padded", "plain_layers")
+                 "bf16_split", "train_bf16_enabled", "strict", "split3_padded", "plain_layers", "square")
 
 
 def _opt(name: str):
@@ -74,7 +77,7 @@ def _opt(name: str):
 def options(**overrides):
     """Context-local dispatch overrides: ``enabled``, ``train_enabled``, ``preproject``, ``preproject_bf16``,
     ``fp32_split3``, ``fp32_split3_train``, ``bf16_split``, ``train_bf16_enabled``, ``strict``, ``split3_padded``,
-    ``plain_layers`` (see ``set_plain_layers``).
+    ``plain_layers`` (see ``set_plain_layers``), ``square`` (see ``set_square``).
     ``strict``: ``concat_mlp`` raises instead of evaluating a Sequential on the library path (see ``set_strict``).
     Nested contexts stack; nothing outside the ``with`` block (or in another thread) sees the change.
     NOTE for training: autograd runs the backward (and the recompute of reentrant checkpoints) on its own worker
@@ -210,6 +213,14 @@ def _pad_grid(h: int) -> int:
     return next(P for P in (32, 64, 128, 256) if 2 * P >= h)
 
 
+def _square_grid(h: int) -> int:
+    """the grid width P whose instantiation a square network of width ``h`` runs on (hgnn_mlp_forward_f32_square): the
+    smallest of 32, 64, 128, 256 with P >= h; 0 = none"""
+    if h % 16 or not 32 <= h <= 256:
+        return 0
+    return next(P for P in (32, 64, 128, 256) if P >= h)
+
+
 def _padded_param(param, rows: int, cols: Optional[int] = None, kept_cols=None, k_cols: Optional[int] = None):
     """zero-padded copy of a Linear / LayerNorm parameter for hgnn_mlp_forward_f32_padded, cached per parameter object
     and version (``_cached``): a weight [out, in] -> [rows, cols] (first layer: only the column blocks ``kept_cols``,
@@ -341,7 +352,25 @@ def _layout_f32_plain(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
     return 16 if small_k else 0, rows, lambda: _f32_params(raw, cols, K, small_k, rows)
 
 
-_LAYOUTS = {"f32": _layout_f32, "f32_plain": _layout_f32_plain, "f32_padded": _layout_f32_padded, "f32_split3": _layout_f32_split3,
+def _layout_f32_square(l, n, lin, ln, raw, cols, K, small_k, hidden, P_grid):
+    """hidden = output (hgnn_mlp_supported_f32_square in include/hgnn_hip.h).  On the grid (hidden == P_grid) a layer as
+    wide as the hidden ones is read as it is; every other layer -- all of them between the grid widths, the narrow last
+    layer of the supernode encoder -- zero padded to P_grid rows, W[l >= 1] to P_grid columns (``_padded_param``)"""
+    if ln is None:
+        return None
+    o, last = int(lin.out_features), l == n - 1
+    if o != hidden and not (last and n == 3 and hidden - 16 < o < hidden and o % 4 == 0):
+        return None
+    if hidden == P_grid and o == hidden:
+        return 16 if small_k else 0, 0, lambda: _f32_params(raw, cols, K, small_k, 0)
+
+    def make():
+        W = _padded_param(lin.weight, P_grid, P_grid if l > 0 else None, cols, 16 if small_k else None)
+        return (W, _padded_param(lin.bias, P_grid), _padded_param(ln.weight, P_grid), _padded_param(ln.bias, P_grid))
+    return 16 if small_k else 0, P_grid if last else 0, make
+
+
+_LAYOUTS = {"f32": _layout_f32, "f32_square": _layout_f32_square, "f32_plain": _layout_f32_plain, "f32_padded": _layout_f32_padded, "f32_split3": _layout_f32_split3,
             "f32_split3_padded": _layout_f32_split3_padded, "bf16": _layout_bf16, "bf16_split": _layout_bf16_split}
 
 
@@ -383,7 +412,7 @@ def _preprojections(tables, cols, proj, lin0, bf16: bool, split_proj: bool, widt
 
 
 def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = False, dry: bool = False, layers=None):
-    """(descriptor, keep-alive list, M, n_out) for ``hgnn_mlp_forward_<entry>`` (``entry`` in f32, f32_padded,
+    """(descriptor, keep-alive list, M, n_out) for ``hgnn_mlp_forward_<entry>`` (``entry`` in f32, f32_padded, f32_square,
     f32_split3, f32_split3_padded, bf16, bf16_split), or None.  ``layers``: ``_parse(net)`` when the caller has it (then ``net`` is not read).
 
     One walk for every kernel: the segments (one row count M, int32 gather indices, pre-projected segments
@@ -412,6 +441,11 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
     P_grid = _pad_grid(hidden) if padded else 0
     if padded and (P_grid == 0 or len(layers) < 2):
         return None
+    pre_width = 2 * P_grid                     # columns of a pre-projected segment's rows: the padded W[0] rows
+    if entry == "f32_square":
+        pre_width = P_grid = _square_grid(hidden)
+        if P_grid == 0:
+            return None
     if bf16:
         pre = _opt("preproject_bf16")
         pre = entry == "bf16_split" and (len(layers) > 1 and hidden >= 512 if pre is None else pre)
@@ -420,7 +454,7 @@ def _descriptor(net, segments, skip, entry: str = "f32", split_proj: bool = Fals
     proj = _projected_segments(segments, M) if pre else []
     tables = [t if t.is_contiguous() else t.contiguous() for t, _ in segments]
     cols = [(sum(ws[:i]), sum(ws[:i + 1])) for i in range(len(ws))]
-    pre_rows = _preprojections(tables, cols, proj, lin0, bf16, split_proj, 2 * P_grid) if proj and not dry else {}
+    pre_rows = _preprojections(tables, cols, proj, lin0, bf16, split_proj, pre_width) if proj and not dry else {}
     d = _lib.HgnnMlpDesc()
     keep = []
     n_kept = n_pre = 0
@@ -820,22 +854,98 @@ class _Route(NamedTuple):
     """what ``_run`` launches for one call (``_route``)"""
     net: nn.Module
     layers: list               # _parse(net)
-    entry: str                 # each launch calls hgnn_mlp_forward_<entry>: f32, f32_split3, bf16, bf16_split, f32_padded
-                               # or f32_split3_padded
+    entry: str                 # each launch calls hgnn_mlp_forward_<entry>: f32, f32_split3, bf16, bf16_split, f32_padded,
+                               # f32_split3_padded, f32_plain or f32_square (with ``groups``: each group's own entry)
     split_proj: bool = False   # f32_split3: pre-projections in the kernel's arithmetic (``_descriptor``)
     chain: bool = False        # one launch per LayerNorm'ed layer (+ a trailing plain Linear)
     head: bool = False         # score head: the plain last Linear runs outside the kernel, on the hidden rows
     train: bool = False        # the differentiable variants (``_FusedMLPTrain``, ``_FusedMLPTrainBf16``)
+    groups: tuple = ()         # 4 to 8 layers: the routes of consecutive launches of at most three layers (``_group_route``)
 
 
-def _route(net, segments, skip, *, train: bool, allow_chain: bool = True) -> Optional[_Route]:  # noqa: C901
+_square = os.environ.get("HGNN_MLP_SQUARE", "1") != "0"
+
+
+def set_square(flag: bool) -> None:
+    """Process default of the ``square`` option (HGNN_MLP_SQUARE=0 switches it off): fp32 networks whose output is as
+    wide as their hidden layers (``hidden_ratio: 1``, ``hidden == latent``; widths: multiples of 16 in [32, 256]), single
+    Linear -> LayerNorm -> act layers of those widths and networks of 4 to 8 layers run on the exact fp32 kernel's square
+    instantiations (hgnn_mlp_forward_f32_square), no-grad and under autograd.  Asked only after every other fp32 route
+    has declined, so no call that had a kernel before changes.  Off: these shapes take the library path (counted in
+    ``stats["library_calls"]``).  A backward and the recompute of a reentrant checkpoint run on autograd's own thread,
+    which only the process default set here reaches.  Default on."""
+    global _square
+    _square = bool(flag)
+
+
+_GROUP_NETS = weakref.WeakKeyDictionary()   # net -> the Sequentials of its groups (sharing its modules)
+
+
+def _group_nets(net, sizes):
+    """``net``'s modules as consecutive Sequentials of ``sizes`` modules, built once per network (again when one of its
+    modules has been replaced)"""
+    mods = list(net)
+    hit = _GROUP_NETS.get(net)
+    if hit is None or hit[0] != sizes or len(hit[2]) != len(mods) or any(a is not b for a, b in zip(hit[2], mods)):
+        subs, i = [], 0
+        for k in sizes:
+            subs.append(nn.Sequential(*mods[i:i + k]))
+            i += k
+        hit = (sizes, subs, mods)
+        _GROUP_NETS[net] = hit
+    for sub in hit[1]:
+        sub._hgnn_split3 = getattr(net, "_hgnn_split3", None)   # models._mark_split3 may run after the first call
+    return hit[1]
+
+
+def _group_route(net, layers, segments, skip, train: bool) -> Optional[_Route]:
+    """Networks of 4 to 8 layers with one hidden width, LayerNorm on every layer, optionally ending in a plain head
+    Linear at most 32 wide: consecutive launches of at most three layers each, the hidden rows between two groups making
+    one trip through HBM.  The first group K -> h -> h -> h carries the segments (square entry), middle groups are
+    square on one direct segment, the last group takes whatever entry accepts its shape and carries ``skip``; a head's
+    plain Linear is a product over the last hidden rows (as for the chains).  Under autograd each group is its own
+    differentiable call.  None: the library path."""
+    plain_last = layers[-1][1] is None
+    body = layers[:-1] if plain_last else layers
+    h = int(layers[0][0].out_features)
+    if not 4 <= len(layers) <= 8 or len(body) < 4 or any(ln is None for _, ln, _ in body) \
+            or any(int(lin.out_features) != h for lin, _, _ in body[:-1]) or not _square_grid(h) \
+            or not isinstance(net, nn.Sequential) or _is_bf16(segments) or not all(t.is_cuda for t, _ in segments):
+        return None
+    if plain_last and (skip is not None or layers[-1][0].out_features > 32 or int(body[-1][0].out_features) != h):
+        return None
+    counts = [3] * ((len(body) - 1) // 3) + [len(body) - 3 * ((len(body) - 1) // 3)]
+    subs = _group_nets(net, tuple(3 * c for c in counts))
+    dev = segments[0][0].device
+    probe = [(torch.empty((0, h), dtype=torch.float32, device=dev), None)]
+    routes = []
+    for i, sub in enumerate(subs):
+        last = i == len(subs) - 1
+        sk = None
+        if last and skip is not None:
+            M = {int(x.numel()) if x is not None else int(t.shape[0]) for t, x in segments}
+            if len(M) != 1 or tuple(skip.shape) != (M.pop(), int(body[-1][0].out_features)) or not skip.is_cuda \
+                    or skip.dtype != torch.float32:
+                return None
+            sk = torch.empty((0, int(skip.shape[1])), dtype=torch.float32, device=dev)
+        r = _route(sub, segments if i == 0 else probe, sk, train=train, allow_groups=False)
+        if r is None or r.chain or (not last and r.entry != "f32_square"):
+            return None
+        routes.append(r)
+    return _Route(net, layers, "f32_square", head=plain_last, train=train, groups=tuple(routes))
+
+
+def _route(net, segments, skip, *, train: bool, allow_chain: bool = True, allow_square: bool = True,  # noqa: C901
+           allow_groups: bool = True) -> Optional[_Route]:
     """The one dispatch decision: which fused kernel evaluates ``net`` on these arguments, or None (library path).
     Parses ``net`` once and asks each kernel's own ``hgnn_mlp_supported*`` check at most once, on a dry descriptor.
 
     ``train=False``: a forward autograd does not record (no grad mode, or nothing requires grad).  fp32 rows: the whole
     network in one launch (hgnn_mlp_forward_f32), else -- ``allow_chain`` -- one launch per layer (latent 512; a caller
     with a cheaper alternative, the bf16 tail of the encoders, passes False), else -- widths between the kernel's
-    template grid -- one launch on zero-padded parameters (hgnn_mlp_forward_f32_padded, exact fp32 only).  Among these, with the split-bf16
+    template grid -- one launch on zero-padded parameters (hgnn_mlp_forward_f32_padded, exact fp32 only), else --
+    ``allow_square``, option ``square`` -- hidden = output, single layers and (``allow_groups``) 4 to 8 layers on
+    hgnn_mlp_forward_f32_square (``square_route``; under autograd too, after f32 and f32_padded).  Among these, with the split-bf16
     arithmetic on (``_split3``): score heads K -> H -> H -> w (H in 256, 512) run their hidden layers on
     hgnn_mlp_forward_f32_split3 and the last Linear as a product over the hidden rows; networks of its shapes run whole
     on it.  bf16 rows: the feature-split kernel where it wants the shape (``bf16_split``) else the plain bf16 kernel,
@@ -909,6 +1019,21 @@ def _route(net, segments, skip, *, train: bool, allow_chain: bool = True) -> Opt
                                 and tuple(skip.shape) == (first[2], layers[-1][0].out_features))
 
     plain_last = layers[-1][1] is None
+
+    def square_route():
+        """asked last, after f32, the chain and f32_padded have declined: hidden = output and single layers on
+        hgnn_mlp_forward_f32_square (the exact kernel also for a module marked for split-bf16), 4 to 8 layers as groups
+        (``_group_route``).  The narrow square encoder has no dumps: it trains on the library path"""
+        if not allow_square or not _opt("square"):
+            return None
+        if len(layers) > 3:
+            return _group_route(net, layers, segments, skip, train) if allow_groups else None
+        if plain_last or not dry("f32_square")[1]:
+            return None
+        if train and layers[-1][0].out_features != layers[0][0].out_features:
+            return None
+        return _Route(net, layers, "f32_square", train=train)
+
     split3_shape = len(layers) in (2, 3) and all(ln is not None for _, ln, _ in layers) and \
         all(t.dtype == torch.float32 and int(t.shape[1]) % 128 == 0 for t, _ in segments)
     if split3_shape:
@@ -930,7 +1055,9 @@ def _route(net, segments, skip, *, train: bool, allow_chain: bool = True) -> Opt
             # widths between the grid's: the same kernel on zero-padded parameters, dumps at the real widths; the
             # backward takes any width (ATen rows where the HIP row kernels have no instantiation)
             return _Route(net, layers, "f32_padded", train=True)
-        if not ok or (int(desc[0].w_last_rows) != 0 and not head):
+        if not ok:
+            return square_route()
+        if int(desc[0].w_last_rows) != 0 and not head:
             return None
         if head and (skip is not None or any(lin.out_features not in (64, 128, 256, 512) for lin, _, _ in layers[:2])):
             return None                                   # widths of the LayerNorm / activation row kernels
@@ -947,7 +1074,7 @@ def _route(net, segments, skip, *, train: bool, allow_chain: bool = True) -> Opt
         # widths between the grid's (latent 48, 96, 160, 192, hidden_ratio 3, ...): zero-padded parameters on the next
         # grid instantiation of the exact fp32 kernel
         if not dry("f32_padded")[1]:
-            return None
+            return square_route()
         if _opt("split3_padded") and _split3(net) and not _narrow_encoder(layers) and dry("f32_split3_padded")[1]:
             # opt-in: the split-bf16 arithmetic on the same zero padding (cell networks with a hidden width above 128)
             return _Route(net, layers, "f32_split3_padded")
@@ -998,6 +1125,8 @@ def _forward(entry, d, out, dev):
         stats["split3_padded_calls"] = stats.get("split3_padded_calls", 0) + 1
     elif entry == "f32_plain":
         stats["plain_calls"] += 1
+    elif entry == "f32_square":
+        stats["square_calls"] += 1
 
 
 def _launch(layers, segments, skip, entry, split_proj=False, out=None):
@@ -1022,6 +1151,18 @@ def _run(r: _Route, segments, skip, out=None):
     tensor (no-grad callers that assemble one edge table from several calls -- the interior / boundary split of a sharded
     edge update -- avoid a 2 GB concatenation); only the single-launch paths write into it directly"""
     layers = r.layers
+    if r.groups:
+        # 4 to 8 layers: one launch (under autograd: one differentiable call) per group, the hidden rows between two
+        # groups make one trip through HBM; the last group carries the skip rows
+        y = None
+        for i, g in enumerate(r.groups):
+            y = _run(g, segments if i == 0 else [(y, None)], skip if i == len(r.groups) - 1 else None)
+        if r.head:
+            hidden, lin = y, layers[-1][0]
+            y = _head_linear(hidden, lin, r.train)
+            if y is None:
+                y = torch.nn.functional.linear(hidden, lin.weight, lin.bias)
+        return y if out is None else out.copy_(y)
     if r.train and r.entry == "f32_plain":
         tables, indices = [t for t, _ in segments], tuple(i for _, i in segments)
         params = [p for lin, _, _ in layers for p in (lin.weight, lin.bias)]

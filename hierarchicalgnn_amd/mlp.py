@@ -33,7 +33,8 @@ def _hybrid(net, segments, skip, train: bool):
             or not all(t.dtype == torch.float32 and t.is_cuda for t, _ in segments):
         return None
     first, rest = nn.Sequential(*list(net)[:3]), nn.Sequential(*list(net)[3:])
-    r_first = fused._route(first, segments, None, train=train)
+    # (the square single layers below 512 are not asked: those encoders keep the routes they have)
+    r_first = fused._route(first, segments, None, train=train, allow_square=False)
     probe = [(torch.empty((0, net[0].out_features), dtype=torch.bfloat16, device=segments[0][0].device), None)]
     r_rest = None if r_first is None else fused._route(rest, probe, None, train=train)
     if r_rest is None:
@@ -64,8 +65,9 @@ def concat_mlp(net: nn.Sequential, segments: Sequence[Segment], skip: Optional[t
     y = _hybrid(net, segments, skip, train=False) if bf16_tail else None
     if y is not None:
         return y
-    r = fused._route(net, segments, skip, train=False, allow_chain=not bf16_tail) \
-        or fused._route(net, segments, skip, train=True)
+    # (bf16 latent mode keeps its bf16 tail where the encoders have no kernel today: the square route is not asked)
+    r = fused._route(net, segments, skip, train=False, allow_chain=not bf16_tail, allow_square=not bf16_tail) \
+        or fused._route(net, segments, skip, train=True, allow_square=not bf16_tail)
     if r is not None:
         return fused._run(r, segments, skip)
     # the same hybrid chain under autograd (encoders at latent 512, whose 1024-wide hidden layers have no fp32 training
@@ -85,7 +87,7 @@ def concat_mlp(net: nn.Sequential, segments: Sequence[Segment], skip: Optional[t
         # under autograd takes the library path, and the two must agree
         seg32 = [(t.float(), i) for t, i in segments]
         skip32 = None if skip is None else skip.float()
-        r = fused._route(net, seg32, skip32, train=False)
+        r = fused._route(net, seg32, skip32, train=False, allow_square=False)   # bf16 rows at hidden = latent: library path
         if r is not None:
             return fused._run(r, seg32, skip32).to(torch.bfloat16)
     if fused._opt("strict"):

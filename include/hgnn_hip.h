@@ -439,6 +439,26 @@ int hgnn_mlp_forward_f32_padded(const hgnn_mlp_desc* d, float* out, hgnn_stream_
 int hgnn_mlp_supported_f32_plain(const hgnn_mlp_desc* d);
 int hgnn_mlp_forward_f32_plain(const hgnn_mlp_desc* d, float* out, hgnn_stream_t stream);
 
+/* SQUARE networks: the output as wide as the hidden layers (hidden_ratio 1, hidden == latent), and single layers below
+ * 512 -- the same exact-fp32 kernel, instantiated with equal tile counts (csrc/mlp_fused_square.hip).  Same descriptor
+ * and segment rules as hgnn_mlp_supported (multiples of 16, or small-K mode with w0_cols = 16; n_pre allowed); fp32
+ * rows, LayerNorm on EVERY layer.  Let h = width[1] (n_layers = 1: the output width), h % 16 == 0, 32 <= h <= 256, and
+ * P = the smallest of {32, 64, 128, 256} with P >= h.
+ *   square:  K -> h (-> h) -> h, n_layers 2 or 3; skip and save_pre allowed;
+ *   narrow:  K -> h -> h -> o with h - 16 < o < h, o % 4 == 0 (the supernode encoder at hidden == latent); no skip, no
+ *            save_pre; out is float[M, o];
+ *   single:  K -> h, one Linear -> LayerNorm -> act (+ skip); save_pre[0] allowed.
+ * width[] carries the REAL widths.  Storage:
+ *   h == P and o == h (square / single on the grid): the parameters as they are; w_last_rows = 0 (or h);
+ *   otherwise (PAD kernels): every layer's W, b, ln_w, ln_b zero padded to P rows (ln_w too), W[l >= 1] also to P
+ *       columns ([P, P]; W[0] is [P, K] or [P, 16]), pre_table[s] is [rows, P] with columns h .. P-1 zero,
+ *       w_last_rows = P, checked.  LayerNorm statistics are masked to the real features; skip, out and save_pre[l]
+ *       rows have their real widths.
+ * Not here: h > 256 (512 / 1024 are hgnn_mlp_supported's single layers), h / 2 < o <= h - 16, heads, bf16 rows.  No
+ * shape of this entry is accepted by another hgnn_mlp_supported*; their verdicts do not depend on it. */
+int hgnn_mlp_supported_f32_square(const hgnn_mlp_desc* d);
+int hgnn_mlp_forward_f32_square(const hgnn_mlp_desc* d, float* out, hgnn_stream_t stream);
+
 /* bf16 variant (BASELINE config 4 dtype) on v_mfma_f32_16x16x32_bf16.  Same descriptor, read as:
  * seg_table / skip / out = bf16 rows; W[l] = bf16 [out][in] row-major, and for l >= 1 with its
  * COLUMNS stored in MFMA k-slot order: column 32c + 8g + j holds input feature

@@ -15,6 +15,11 @@ hgnn_mlp_forward_f32_split3_padded) against the route with the option off in the
 and the native neighbour's split-bf16 default (latent 256: also its 64-row kernel, which is what the padded entry
 launches, next to the 128-row tile); the same three rows.
 
+``--square``: hidden = latent (``hidden_ratio: 1``) on the square route (hgnn_mlp_forward_f32_square): the edge update
+3L -> L -> L and the node update 2L -> L -> L -> L at latent 128 and 256, M = 2M rows, against what these shapes ran on
+before they had a kernel -- the library path (``fused.set_enabled(False)``).  ``beats_library_by_3x_spread``: the medians
+differ by more than three times the larger (max - min) spread of the two variants.
+
 Method: device events around ``--inner`` back-to-back calls, every variant warmed up first, the variants ALTERNATED
 inside each of ``--repeats`` (>= 7) rounds; per variant the median per-call time and the spread (min, max) over the
 rounds.  One JSON document on stdout (``--out FILE`` also writes it).
@@ -186,6 +191,37 @@ def ec_in_split3(L, x, ei, repeats):
                 split3_vs_exact_max_abs_score=diff, **res)
 
 
+def square_update(L, kind, graph, N, repeats, inner):
+    """hidden = latent: ``kind`` "edge" (3L -> L -> L on gathered node rows + edge rows, Tanh output) or "node"
+    (2L -> L -> L -> L on M direct rows, GELU output), skip connection on the last segment"""
+    M = int(graph.shape[1])
+    torch.manual_seed(L)
+    rows = torch.randn(M, L, device="cuda")
+    if kind == "edge":
+        net = make_mlp(3 * L, L, L, 2, layer_norm=True, output_activation="Tanh", hidden_activation="GELU").cuda()
+        nodes = torch.randn(N, L, device="cuda")
+        segs = [(nodes, graph[0]), (nodes, graph[1]), (rows, None)]
+        shape = f"edge update 3x{L} -> {L} -> {L}, M = {M}, N = {N}"
+    else:
+        net = make_mlp(2 * L, L, L, 3, layer_norm=True, output_activation="GELU", hidden_activation="GELU").cuda()
+        segs = [(rows, None), (torch.randn(M, L, device="cuda"), None)]
+        shape = f"node update 2x{L} -> {L} -> {L} -> {L}, M = {M}"
+    own = lambda: mlp.concat_mlp(net, segs, skip=rows)   # noqa: E731
+    with torch.no_grad():
+        n0 = fused.stats.get("square_calls", 0)
+        a = own()
+        ran = fused.stats.get("square_calls", 0) == n0 + 1
+        b = _library(own)()
+        err = float((a - b).abs().max() / b.abs().max())
+        del a, b
+        res = _alternate({"square": own, "library": _library(own)}, repeats, inner)
+    sq, lib = res["square"], res["library"]
+    spread = max(sq["max_ms"] - sq["min_ms"], lib["max_ms"] - lib["min_ms"])
+    return dict(shape=shape, square_kernel_ran=ran, square_vs_library_max_rel=err,
+                speedup=round(lib["median_ms"] / sq["median_ms"], 3),
+                beats_library_by_3x_spread=bool(lib["median_ms"] - sq["median_ms"] > 3 * spread), **res)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--repeats", type=int, default=9)
@@ -196,6 +232,9 @@ def main():
     ap.add_argument("--split3", action="store_true",
                     help="measure the opt-in split-bf16 route at these widths against the exact padded one "
                          "(default --out: profiles/mlp_widths_split3_bench.json)")
+    ap.add_argument("--square", action="store_true",
+                    help="measure hidden = latent on the square route against the library path "
+                         "(default --out: profiles/mlp_square.json)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_mlp_widths: needs a GPU (there is no CPU path to time)")
@@ -206,7 +245,13 @@ def main():
     graph = synth.directed(ei).cuda()
     head = dict(device=torch.cuda.get_device_name(0), repeats=args.repeats, inner=args.inner,
                 method="device events, variants alternated inside each repeat, median (min, max) per call")
-    if args.split3:
+    if args.square:
+        if args.out is None:
+            args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                    "mlp_square.json")
+        doc = dict(**head, updates=[square_update(L, kind, graph, args.nodes, args.repeats, args.inner)
+                                    for L in (128, 256) for kind in ("edge", "node")])
+    elif args.split3:
         if args.out is None:
             args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                     "mlp_widths_split3_bench.json")
