@@ -7,6 +7,8 @@ Drop-in surface (same names / signatures as the reference):
     InteractionGNNCell(hparams), HierarchicalGNNCell(hparams)   <- Modules/gnn_utils.py
     make_mlp(...)                                        <- Modules/utils.py
     eval_metrics(bipartite_graph, event, ...)            <- Modules/tracking_utils.py
+    track_records(bipartite_graph, event, bins, ...)     eval_metrics plus per-particle / per-candidate tables and
+                                                         binned counts (no counterpart in the reference)
     graph_intersection(...), frnn_graph(...)             <- Modules/utils.py (embedding stage)
     bipartite_loss(...), bc_training_loss(...)           <- BipartiteClassificationBase.get_bipartite_loss / training_step
     pair_hinge_loss(...), embedding_hgnn_training_loss(...)   <- EmbeddingBase.training_step's weighted hinge loss
@@ -26,7 +28,7 @@ from .plan import GraphPlan, get_plan, clear_plan_cache, plan_cache_stats  # noq
 from .utils import make_mlp  # noqa: F401
 from .gnn_utils import InteractionGNNCell, HierarchicalGNNCell  # noqa: F401
 from .tracking import eval_metrics, edge_track_candidates, bipartite_track_candidates  # noqa: F401
-from .tracking import embedding_track_candidates  # noqa: F401
+from .tracking import embedding_track_candidates, track_records  # noqa: F401
 from .hdbscan import hdbscan, hdbscan_tree  # noqa: F401  (the name `hdbscan` is the function; the module is
 #                                             importlib.import_module("hierarchicalgnn_amd.hdbscan"))
 from .embedding import frnn_graph, graph_intersection, training_samples, training_weights, hinge_distance  # noqa: F401

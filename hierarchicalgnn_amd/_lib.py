@@ -28,6 +28,8 @@ DT_F32, DT_BF16, DT_I32, DT_I64, DT_F64 = 0, 1, 2, 3, 4   # HGNN_DT_*
 # HGNN_TE_*: entries of hgnn_track_eval's result vector
 (TE_TRACK_EFF, TE_TRACK_PUR, TE_HIT_EFF, TE_HIT_PUR, TE_N_KEPT, TE_N_MASK, TE_N_TRUTH, TE_N_CAND, TE_N_PART,
  TE_NO_MATCH, TE_STATUS, TE_N_MATCH, TE_RESULT) = range(13)
+# HGNN_TR_*: hgnn_track_records' limits and histogram columns
+TR_MAX_VARS, TR_MAX_BINS, TR_COLUMNS = 4, 64, 6
 
 # HGNN_AM_*: hgnn_assign_match's constants, status bits and the entries of its info vector
 AM_SCALE_BITS, AM_FALLBACK_WEIGHT = 30, 1e-12
@@ -107,6 +109,17 @@ class HgnnOptEntry(Structure):
         ("decay", c_float), ("step_size", c_float), ("inv_sqrt_bc2", c_float), ("one_minus_b1", c_float),
         ("b2", c_float), ("one_minus_b2", c_float), ("eps", c_float), ("reserved", c_int32),
     ]
+
+
+class HgnnTrParticles(Structure):
+    """mirror of ``struct hgnn_tr_particles``"""
+    _fields_ = [(k, c_void_p) for k in ("pid", "nhits", "pt", "primary", "reconstructable", "n_match", "n_kept",
+                                        "n_mask", "cand_index", "shared", "values")]
+
+
+class HgnnTrCandidates(Structure):
+    """mirror of ``struct hgnn_tr_candidates``"""
+    _fields_ = [(k, c_void_p) for k in ("label", "size", "n_kept", "n_mask", "particle", "shared")]
 
 
 _SIGNATURES = {
@@ -208,6 +221,11 @@ _SIGNATURES = {
     "hgnn_track_eval_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
     "hgnn_track_eval": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double,
                                 c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hgnn_track_records_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, POINTER(c_size_t)]),
+    "hgnn_track_records": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                   c_int32, POINTER(c_float), POINTER(c_int32), c_double, c_double, c_double,
+                                   c_void_p, POINTER(HgnnTrParticles), POINTER(HgnnTrCandidates), c_void_p, c_void_p,
+                                   c_size_t, c_void_p]),
     "hgnn_graph_intersection_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, POINTER(c_size_t)]),
     "hgnn_graph_intersection": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

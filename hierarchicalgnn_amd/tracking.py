@@ -6,6 +6,11 @@ cugraph (EdgeClassifier/edge_classifier_base.py:157-168); neither exists on ROCm
     eval_metrics(bipartite_graph, event, ...)      same signature and return dict as the reference; one call of
                                                    ``hgnn_track_eval`` (csrc/trackeval.hip) and ONE host read, the
                                                    12-double result vector
+    track_records(bipartite_graph, event, bins, ...)
+                                                   the same metrics with the per-particle table, the per-candidate
+                                                   table and integer histograms over chosen variables: one call of
+                                                   ``hgnn_track_records`` (csrc/trackeval_records.hip), the same ONE
+                                                   host read
     edge_track_candidates(edge_index, scores, score_cut, inverse_mask)
                                                    edge_classifier_base.py:157-168: components of the edges above
                                                    the cut (all edges when none passes), lock-free union-find
@@ -19,6 +24,7 @@ There is no CPU path: every input must be a HIP device tensor.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 
 import torch
@@ -45,31 +51,37 @@ def _has(event, name) -> bool:
     return name in event if isinstance(event, dict) or hasattr(event, "__contains__") else hasattr(event, name)
 
 
-def track_eval(bipartite_graph: torch.Tensor, event, pt_cut: float = 1., nhits_cut=5, majority_cut: float = 0.5,
-               primary: bool = True) -> torch.Tensor:
-    """``hgnn_track_eval``: the float64[HGNN_TE_RESULT] device result vector (indices ``_lib.TE_*``), without a
-    host read.  ``primary=True`` needs an ``event.primary`` field: any hit of a particle with primary != 0 makes
-    the particle primary (what the reference's dead ``primary=True`` branch intends)."""
+def _inputs(who: str, bipartite_graph: torch.Tensor, event, majority_cut, primary):
+    """the checked operands of ``hgnn_track_eval`` / ``hgnn_track_records``: (hit, cand, pid, pt, prim or None)"""
     pid, pt = _field(event, "pid"), _field(event, "pt")
     if not (bipartite_graph.is_cuda and pid.is_cuda and pt.is_cuda):
-        raise RuntimeError("eval_metrics needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
+        raise RuntimeError(f"{who} needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
     if bipartite_graph.dim() != 2 or bipartite_graph.shape[0] != 2:
-        raise ValueError(f"eval_metrics: bipartite_graph must be [2, B], got {tuple(bipartite_graph.shape)}")
+        raise ValueError(f"{who}: bipartite_graph must be [2, B], got {tuple(bipartite_graph.shape)}")
     if not float(majority_cut) > 0:
-        raise ValueError("eval_metrics: majority_cut must be > 0")
+        raise ValueError(f"{who}: majority_cut must be > 0")
     prim = None
     if primary:
         if not _has(event, "primary"):
-            raise ValueError("eval_metrics(primary=True): the event has no `primary` field "
+            raise ValueError(f"{who}(primary=True): the event has no `primary` field "
                              "(pass primary=False, as every reference training base does)")
         prim = _field(event, "primary").reshape(-1).ne(0).to(torch.uint8)
-    dev = bipartite_graph.device
     hit = bipartite_graph[0].to(torch.int64).contiguous()
     cand = bipartite_graph[1].to(torch.int64).contiguous()
     pid = pid.reshape(-1).to(torch.int64).contiguous()
     pt = pt.reshape(-1).to(torch.float32).contiguous()
     if pt.numel() != pid.numel() or (prim is not None and prim.numel() != pid.numel()):
-        raise ValueError("eval_metrics: event.pid, event.pt (and event.primary) must have one entry per hit")
+        raise ValueError(f"{who}: event.pid, event.pt (and event.primary) must have one entry per hit")
+    return hit, cand, pid, pt, prim
+
+
+def track_eval(bipartite_graph: torch.Tensor, event, pt_cut: float = 1., nhits_cut=5, majority_cut: float = 0.5,
+               primary: bool = True) -> torch.Tensor:
+    """``hgnn_track_eval``: the float64[HGNN_TE_RESULT] device result vector (indices ``_lib.TE_*``), without a
+    host read.  ``primary=True`` needs an ``event.primary`` field: any hit of a particle with primary != 0 makes
+    the particle primary (what the reference's dead ``primary=True`` branch intends)."""
+    hit, cand, pid, pt, prim = _inputs("eval_metrics", bipartite_graph, event, majority_cut, primary)
+    dev = bipartite_graph.device
     lib = _lib.load()
     ws, nb = _lib.workspace("hgnn_track_eval_workspace_bytes", dev, hit.numel(), pid.numel())
     result = torch.empty(_lib.TE_RESULT, dtype=torch.float64, device=dev)
@@ -112,6 +124,111 @@ def eval_metrics(bipartite_graph, event, pt_cut=1., nhits_cut=5, majority_cut=0.
         "hit_eff": r[_lib.TE_HIT_EFF],
         "hit_pur": r[_lib.TE_HIT_PUR],
     }
+
+
+PARTICLE_FIELDS = (("pid", torch.int64), ("nhits", torch.int32), ("pt", torch.float32), ("primary", torch.uint8),
+                   ("reconstructable", torch.uint8), ("n_match", torch.int32), ("n_kept", torch.int32),
+                   ("n_mask", torch.int32), ("cand_index", torch.int32), ("shared", torch.int32))
+CANDIDATE_FIELDS = (("label", torch.int64), ("size", torch.int32), ("n_kept", torch.int32), ("n_mask", torch.int32),
+                    ("particle", torch.int32), ("shared", torch.int32))
+# the columns of a histogram slot, in order
+BIN_COLUMNS = ("particles", "reconstructable", "n_kept", "n_mask", "masked_shared", "masked_nhits")
+COUNT_KEYS = ("n_kept", "n_mask", "n_truth", "n_cand", "n_part", "n_match")
+
+
+def _edges_f32(name, edges) -> torch.Tensor:
+    """the edges of one variable as a host float32 tensor, rounded once, checked after the rounding"""
+    e = torch.as_tensor(edges)
+    if e.is_cuda:
+        raise ValueError(f"track_records: the edges of bins[{name!r}] must be host values (a sequence or a CPU tensor)")
+    e = e.detach().reshape(-1).to(torch.float64).to(torch.float32)
+    if not 2 <= e.numel() <= _lib.TR_MAX_BINS + 1:
+        raise ValueError(f"track_records: bins[{name!r}] needs 2..{_lib.TR_MAX_BINS + 1} edges, got {e.numel()}")
+    if not bool(torch.isfinite(e).all()):
+        raise ValueError(f"track_records: the edges of bins[{name!r}] must be finite in float32")
+    if not bool((e[1:] > e[:-1]).all()):
+        raise ValueError(f"track_records: the edges of bins[{name!r}] must be strictly ascending in float32")
+    return e
+
+
+def track_records(bipartite_graph, event, bins=None, pt_cut=1., nhits_cut=5, majority_cut=0.5, primary=True):
+    """``eval_metrics`` with what it folds away (``hgnn_track_records``, csrc/trackeval_records.hip): the metrics, a
+    per-particle table, a per-candidate table and integer histograms of the particles over chosen variables, from
+    one call and ONE host read (the same 12-double result vector).
+
+    bins: ``{name: (values, edges)}``, at most four.  ``values`` is a per-hit device tensor or the name of an event
+    field; a particle's value is the minimum over its hits in which a NaN wins, as its ``pt`` is.  ``edges``: 2..65
+    finite, strictly ascending host numbers, rounded to float32 once.  Slot = number of edges <= value in float32
+    (``numpy.searchsorted(edges, x, "right")``): 0 is the underflow, nb + 1 the overflow, where a NaN lands.
+
+    Returns ``{"metrics": what eval_metrics returns, "counts": the integer HGNN_TE_N_* entries,
+    "particles": {field: tensor[P]} in ascending pid (PARTICLE_FIELDS and ``values``, float32 [V, P]),
+    "candidates": {field: tensor[C]} in ascending label (CANDIDATE_FIELDS),
+    "bins": {name: {"edges": float32[nb + 1], "counts": int64[nb + 2, 6]}}}`` (columns: BIN_COLUMNS); every tensor
+    is on the device."""
+    # the host-side argument checks come first (they need no device), then the device refusals
+    bins = {} if bins is None else dict(bins)
+    V = len(bins)
+    if V > _lib.TR_MAX_VARS:
+        raise ValueError(f"track_records: at most {_lib.TR_MAX_VARS} binning variables, got {V}")
+    n_hits = _field(event, "pid").numel()
+    edges_host = torch.zeros((max(V, 1), _lib.TR_MAX_BINS + 1), dtype=torch.float32)
+    n_bins = (ctypes.c_int32 * max(V, 1))()
+    columns = []
+    for v, (name, spec) in enumerate(bins.items()):
+        try:
+            values, edges = spec
+        except (TypeError, ValueError):
+            raise ValueError(f"track_records: bins[{name!r}] must be (values, edges)") from None
+        if isinstance(values, str):
+            values = _field(event, values)
+        if not isinstance(values, torch.Tensor):
+            raise ValueError(f"track_records: the values of bins[{name!r}] must be a tensor or an event field name")
+        if values.numel() != n_hits:
+            raise ValueError(f"track_records: the values of bins[{name!r}] must have one entry per hit "
+                             f"({n_hits}), got {values.numel()}")
+        e = _edges_f32(name, edges)
+        edges_host[v, :e.numel()] = e
+        n_bins[v] = e.numel() - 1
+        columns.append(values)
+    hit, cand, pid, pt, prim = _inputs("track_records", bipartite_graph, event, majority_cut, primary)
+    if not all(x.is_cuda for x in columns):
+        raise RuntimeError("track_records needs HIP device tensors: hierarchicalgnn_amd has no CPU path "
+                           "(the values of a binning variable are on the host)")
+    dev = bipartite_graph.device
+    B, N = hit.numel(), pid.numel()
+    vars_ = torch.stack([x.detach().reshape(-1).to(torch.float32) for x in columns]).contiguous() if V else None
+    lib = _lib.load()
+    ws, nb = _lib.workspace("hgnn_track_records_workspace_bytes", dev, B, N, V)
+    result = torch.empty(_lib.TE_RESULT, dtype=torch.float64, device=dev)
+    ptab = {k: torch.empty(N, dtype=dt, device=dev) for k, dt in PARTICLE_FIELDS}
+    ptab["values"] = torch.empty((V, N), dtype=torch.float32, device=dev)
+    ctab = {k: torch.empty(B, dtype=dt, device=dev) for k, dt in CANDIDATE_FIELDS}
+    hist = torch.empty((V, _lib.TR_MAX_BINS + 2, _lib.TR_COLUMNS), dtype=torch.int64, device=dev)
+    cp = _lib.HgnnTrParticles(**{k: _lib.ptr(t) for k, t in ptab.items()})
+    cc = _lib.HgnnTrCandidates(**{k: _lib.ptr(t) for k, t in ctab.items()})
+    with torch.cuda.device(dev):
+        _lib.check(lib.hgnn_track_records(
+            _lib.ptr(hit), _lib.ptr(cand), B, _lib.ptr(pid), _lib.ptr(pt), _lib.ptr(prim) if prim is not None else None,
+            N, _lib.ptr(vars_), V, ctypes.cast(edges_host.data_ptr(), ctypes.POINTER(ctypes.c_float)), n_bins,
+            float(pt_cut), float(nhits_cut), float(majority_cut), _lib.ptr(result), ctypes.byref(cp), ctypes.byref(cc),
+            _lib.ptr(hist), _lib.ptr(ws), nb, _lib.current_stream(dev)), "hgnn_track_records")
+        edges_dev = edges_host.pin_memory().to(dev, non_blocking=True) if V else None
+    r = read_result(result)
+    P, C = int(r[_lib.TE_N_PART]), int(r[_lib.TE_N_CAND])
+    if r[_lib.TE_NO_MATCH] != 0:
+        metrics = dict(default_response)
+    else:
+        metrics = {"track_eff": r[_lib.TE_TRACK_EFF], "track_pur": r[_lib.TE_TRACK_PUR],
+                   "hit_eff": r[_lib.TE_HIT_EFF], "hit_pur": r[_lib.TE_HIT_PUR]}
+    counts = {k: int(r[getattr(_lib, "TE_" + k.upper())]) for k in COUNT_KEYS}
+    particles = {k: (t[:, :P] if k == "values" else t[:P]) for k, t in ptab.items()}
+    candidates = {k: t[:C] for k, t in ctab.items()}
+    out_bins = {}
+    for v, name in enumerate(bins):
+        n = int(n_bins[v])
+        out_bins[name] = {"edges": edges_dev[v, :n + 1], "counts": hist[v, :n + 2]}
+    return {"metrics": metrics, "counts": counts, "particles": particles, "candidates": candidates, "bins": out_bins}
 
 
 def edge_track_candidates(edge_index: torch.Tensor, scores: torch.Tensor, score_cut, inverse_mask: torch.Tensor):

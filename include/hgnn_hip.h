@@ -53,7 +53,8 @@ extern "C" {
 /* hgnn_assign_match and hgnn_assign_match_workspace_bytes were added without a bump: they are additions, and
  * no existing entry point, struct or constant changed layout or meaning.  The same holds for
  * hgnn_segment_reduce_f32_ex, hgnn_plan_item_order(_workspace_bytes), hgnn_get_option and the optimiser step
- * (hgnn_optim_*, hgnn_sizeof_opt_entry, struct hgnn_opt_entry, HGNN_OPT_*) and for hgnn_wgrad_f32(_workspace_bytes). */
+ * (hgnn_optim_*, hgnn_sizeof_opt_entry, struct hgnn_opt_entry, HGNN_OPT_*), for hgnn_wgrad_f32(_workspace_bytes) and for
+ * hgnn_track_records(_workspace_bytes) with struct hgnn_tr_particles, struct hgnn_tr_candidates and HGNN_TR_*. */
 #define HGNN_ABI_VERSION 26
 
 typedef void* hgnn_stream_t; /* hipStream_t */
@@ -731,6 +732,68 @@ int hgnn_track_eval_workspace_bytes(int64_t n_pairs, int64_t n_hits, size_t* byt
 int hgnn_track_eval(const int64_t* hit, const int64_t* cand, int64_t n_pairs, const int64_t* pid, const float* pt,
                     const uint8_t* primary, int64_t n_hits, double pt_cut, double nhits_cut, double majority_cut,
                     double* result, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
+
+/* hgnn_track_records: hgnn_track_eval's pipeline (the same sorts, contingency triples and match rule), keeping
+ *   what that entry folds into its 12 doubles.  Added under ABI 26: additions only.  The arguments shared with
+ *   hgnn_track_eval mean the same, and result[HGNN_TE_*] has the same bits for the same inputs.
+ *   Particle table (struct hgnn_tr_particles, device arrays of n_hits rows; rows p < P = result[HGNN_TE_N_PART]
+ *   are written, in ascending pid; the other rows are unspecified): pid; nhits; pt, the minimum over the
+ *   particle's hits in which a NaN wins (and -0.0 is below 0.0, so the bits do not depend on the order); primary (any hit primary; 0 with primary == NULL); reconstructable
+ *   (pt > float(pt_cut), nhits >= nhits_cut and, with primary, primary: the particles HGNN_TE_N_TRUTH counts, the
+ *   noise particle pid 0 included as there); n_match / n_kept / n_mask, the particle's matches before the filter,
+ *   kept by it, and kept and reconstructable; cand_index, the SMALLEST dense candidate index among its kept
+ *   matches, or -1, and shared, that triple's pair count n, or 0 (a particle can keep two matches: for C above
+ *   about 4500 neighbouring hash values round to the same double); values [n_vars][n_hits], every binning variable
+ *   reduced over the particle's hits exactly as pt is.
+ *   Candidate table (struct hgnn_tr_candidates, device arrays of n_pairs rows; rows c < C = result[HGNN_TE_N_CAND]
+ *   are written, in ascending label): label, the original label; size, its pairs (duplicates counted); n_kept /
+ *   n_mask, the kept and the masked matches that name it; particle, the SMALLEST particle row among its kept
+ *   matches, or -1, and shared, that triple's n, or 0 (with majority_cut <= 0.5 two particles can hold one
+ *   candidate).
+ *   Binning: vars is device float32 [n_vars][n_hits] (NULL with n_vars == 0), 0 <= n_vars <= HGNN_TR_MAX_VARS.
+ *   edges (float32 [n_vars][HGNN_TR_MAX_BINS + 1]) and n_bins (int32 [n_vars], each in [1, HGNN_TR_MAX_BINS])
+ *   are HOST arrays, read before the call returns; the first n_bins[v] + 1 edges of row v are used and must be
+ *   finite and strictly ascending.  The slot of particle p for variable v is the number of edges <= values[v][p],
+ *   compared in float32 (numpy.searchsorted(edges, x, side="right")): slot 0 is the underflow, 1 .. nb the bins,
+ *   nb + 1 the overflow, where a NaN lands too.  hist is device int64 [n_vars][HGNN_TR_MAX_BINS + 2]
+ *   [HGNN_TR_COLUMNS] (slots above nb + 1 stay 0); the columns of a slot: particles, reconstructable particles,
+ *   sum of n_kept, sum of n_mask, sum of n over the masked triples, sum of nhits * n_mask.  Over all slots the
+ *   first four add up to HGNN_TE_N_PART, N_TRUTH, N_KEPT and N_MASK (with n_pairs == 0 result[] is the default
+ *   response and says N_TRUTH = 0, while the particle table and the first two columns are still filled).
+ *   A hit id outside [0, n_hits) does not fault: result[HGNN_TE_STATUS] = 1 and everything else is meaningless.
+ *   Integer counting only (integer atomics on the candidate side and in the histogram): two calls give the same
+ *   bits.  Allocates nothing; launches on `stream`.
+ * hgnn_track_records_workspace_bytes: device scratch of one call (any 256-B aligned). */
+#define HGNN_TR_MAX_VARS 4
+#define HGNN_TR_MAX_BINS 64
+#define HGNN_TR_COLUMNS 6
+struct hgnn_tr_particles {
+    int64_t* pid;
+    int32_t* nhits;
+    float* pt;
+    uint8_t* primary;
+    uint8_t* reconstructable;
+    int32_t* n_match;
+    int32_t* n_kept;
+    int32_t* n_mask;
+    int32_t* cand_index;
+    int32_t* shared;
+    float* values; /* [n_vars][n_hits]; NULL with n_vars == 0 */
+};
+struct hgnn_tr_candidates {
+    int64_t* label;
+    int32_t* size;
+    int32_t* n_kept;
+    int32_t* n_mask;
+    int32_t* particle;
+    int32_t* shared;
+};
+int hgnn_track_records_workspace_bytes(int64_t n_pairs, int64_t n_hits, int32_t n_vars, size_t* bytes);
+int hgnn_track_records(const int64_t* hit, const int64_t* cand, int64_t n_pairs, const int64_t* pid, const float* pt,
+                       const uint8_t* primary, int64_t n_hits, const float* vars, int32_t n_vars, const float* edges,
+                       const int32_t* n_bins, double pt_cut, double nhits_cut, double majority_cut, double* result,
+                       const struct hgnn_tr_particles* particles, const struct hgnn_tr_candidates* candidates,
+                       int64_t* hist, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * graph_intersection of the embedding stage (reference Modules/utils.py:117-166, scipy CSR there).  ABI 26.
