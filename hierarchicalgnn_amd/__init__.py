@@ -10,6 +10,7 @@ Drop-in surface (same names / signatures as the reference):
     track_records(bipartite_graph, event, bins, ...)     eval_metrics plus per-particle / per-candidate tables and
                                                          binned counts (no counterpart in the reference)
     graph_intersection(...), frnn_graph(...)             <- Modules/utils.py (embedding stage)
+    training_samples(...), training_pairs(knn_idx, ...)  <- EmbeddingBase.get_training_samples (the second: from the kNN matrix)
     bipartite_loss(...), bc_training_loss(...)           <- BipartiteClassificationBase.get_bipartite_loss / training_step
     pair_hinge_loss(...), embedding_hgnn_training_loss(...)   <- EmbeddingBase.training_step's weighted hinge loss
     weighted_bce_loss(...), ec_training_loss(...), ec_shared_evaluation(...)   <- EdgeClassifierBase.training_step / shared_evaluation
@@ -32,6 +33,7 @@ from .tracking import embedding_track_candidates, track_records  # noqa: F401
 from .hdbscan import hdbscan, hdbscan_tree  # noqa: F401  (the name `hdbscan` is the function; the module is
 #                                             importlib.import_module("hierarchicalgnn_amd.hdbscan"))
 from .embedding import frnn_graph, graph_intersection, training_samples, training_weights, hinge_distance  # noqa: F401
+from .embedding import training_pairs  # noqa: F401
 from .embedding import (pair_hinge_loss, pair_hinge_check, embedding_hgnn_training_loss,  # noqa: F401
                         embedding_in_training_loss)
 from .assignment import (max_weight_matching, bipartite_loss, bc_embedding_loss, bc_training_loss,  # noqa: F401

@@ -70,6 +70,12 @@ EP_ST_BAD_ID = 1
 EP_NOISE, EP_REMOVE_ISOLATED, EP_USE_PRIMARY = 1, 2, 4
 EP_N_NODES, EP_E_EDGE_INDEX, EP_E_MODULEWISE, EP_E_SIGNAL, EP_STATUS = range(5)
 EP_INFO = 8
+# HGNN_TP_*: hgnn_training_pairs_*'s limit, modes, status bits and device info vector
+TP_MAX_K = 128
+TP_MODE_MODULEWISE, TP_MODE_PID = 0, 1
+TP_ST_BAD_IDX, TP_ST_BAD_MTE = 1, 2
+TP_P, TP_N_ROW, TP_N_TRUTH, TP_STATUS = range(4)
+TP_INFO = 4
 
 class HgnnPlan(Structure):
     """mirror of ``struct hgnn_plan``"""
@@ -279,6 +285,11 @@ _SIGNATURES = {
     "hgnn_event_edges_fill": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                       c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "hgnn_event_gather_rows": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "hgnn_training_pairs_workspace_bytes": (c_int, [c_int64, c_int32, c_int64, c_int32, POINTER(c_size_t)]),
+    "hgnn_training_pairs_count": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int32,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hgnn_training_pairs_fill": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int32,
+                                         c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

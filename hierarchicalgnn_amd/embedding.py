@@ -10,7 +10,12 @@ fixed-radius kNN graph of the embeddings with knn = 100 (frnn, CUDA-only, there)
     graph_intersection(pred_graph, truth_graph, using_weights=False, weights_bidir=None)
                                                      utils.graph_intersection: one hgnn_graph_intersection call
                                                      (csrc/intersect.hip) and ONE host read (the count and status)
-    training_samples(embeddings, batch, hparams)     EmbeddingBase.get_training_samples, both true_edges modes
+    training_samples(embeddings, batch, hparams, prediction_graph=None, fused=False)
+                                                     EmbeddingBase.get_training_samples, both true_edges modes;
+                                                     fused=True: knn_radius + training_pairs, the same bits
+    training_pairs(knn_idx, batch, hparams)          the same from the kNN matrix [N, K <= 128], row by row
+                                                     (csrc/trainpairs.hip): no [2, N*K] graph, no sort of the pairs,
+                                                     ONE host read (the sizes and the status)
     training_weights(batch, graph, y, hparams)       pt_weighting + get_training_weight (:95-107, :137-146)
     hinge_distance(embeddings, graph, y)             get_hinge_distance (:148-155)
     pair_hinge_loss(embeddings, graph, y, batch, hparams, margin=None, scale=1.0)
@@ -118,11 +123,105 @@ def _knn_method(hparams):
     return hparams["knn_method"] if "knn_method" in hparams else None
 
 
-def training_samples(embeddings, batch, hparams, prediction_graph=None):
+_TP_MODES = {"modulewise_true_edges": _lib.TP_MODE_MODULEWISE, "pid_true_edges": _lib.TP_MODE_PID}
+
+
+def training_pairs(knn_idx, batch, hparams):
+    """``training_samples`` from the kNN matrix itself: (graph int64 [2, P], y bool [P]), bit-equal to
+    ``training_samples(..., prediction_graph=<the pairs (row, id) of the valid slots of knn_idx, row-major>)``, pair
+    order included, in both ``hparams["true_edges"]`` modes -- without that [2, N*K] graph, without a sort of the
+    pairs and with ONE host read (the sizes and the status, counted in ``stats["host_reads"]``); csrc/trainpairs.hip.
+
+    ``knn_idx`` int64 [N, K], 1 <= K <= 128 (``ops.knn_radius``'s): ids in [0, N), -1 = an empty slot, anywhere in a
+    row; duplicates within a row are allowed.  ``batch``: ``modulewise_true_edges`` int64 [2, T], ``signal_mask`` bool
+    [N], ``pid`` int64 [N], on knn_idx's device.  Both results are contiguous and exactly sized.  ValueError for a
+    wrong dtype or shape, tensors on different devices or an unknown mode (before any launch), and, after the read,
+    for an entry of knn_idx outside [-1, N) or an id of modulewise_true_edges outside [0, N) (such an id is skipped by
+    the kernels and never used as an address).  RuntimeError for CPU tensors: there is no CPU path."""
+    mte = _field(batch, "modulewise_true_edges")
+    signal_mask = _field(batch, "signal_mask")
+    pid = _field(batch, "pid")
+    for t, name in ((knn_idx, "knn_idx"), (mte, "modulewise_true_edges"), (signal_mask, "signal_mask"), (pid, "pid")):
+        if not torch.is_tensor(t):
+            raise ValueError(f"training_pairs: {name} must be a tensor")
+    if knn_idx.dtype != torch.int64 or knn_idx.dim() != 2:
+        raise ValueError(f"training_pairs: knn_idx must be int64 [N, K], got {knn_idx.dtype} {tuple(knn_idx.shape)}")
+    n, k = int(knn_idx.shape[0]), int(knn_idx.shape[1])
+    if not 1 <= k <= _lib.TP_MAX_K:
+        raise ValueError(f"training_pairs: K = {k} must be in [1, {_lib.TP_MAX_K}]")
+    if mte.dtype != torch.int64 or mte.dim() != 2 or mte.shape[0] != 2:
+        raise ValueError(f"training_pairs: modulewise_true_edges must be int64 [2, T], got {mte.dtype} "
+                         f"{tuple(mte.shape)}")
+    if signal_mask.dtype != torch.bool or tuple(signal_mask.shape) != (n,):
+        raise ValueError(f"training_pairs: signal_mask must be bool [N = {n}], got {signal_mask.dtype} "
+                         f"{tuple(signal_mask.shape)}")
+    if pid.dtype != torch.int64 or tuple(pid.shape) != (n,):
+        raise ValueError(f"training_pairs: pid must be int64 [N = {n}], got {pid.dtype} {tuple(pid.shape)}")
+    dev = knn_idx.device
+    if mte.device != dev or signal_mask.device != dev or pid.device != dev:
+        raise ValueError("training_pairs: knn_idx, modulewise_true_edges, signal_mask and pid must be on one device")
+    mode = hparams["true_edges"]
+    if mode not in _TP_MODES:
+        raise ValueError(f"training_pairs: true_edges must be 'modulewise_true_edges' or 'pid_true_edges', "
+                         f"got {mode!r}")
+    t = int(mte.shape[1])
+    if n * k + 2 * t >= 2 ** 31 or t >= 2 ** 29:
+        raise ValueError(f"training_pairs: N * K + 2 T = {n * k + 2 * t} must stay below 2^31 (and T below 2^29)")
+    if not knn_idx.is_cuda:
+        raise RuntimeError("training_pairs needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
+    if n == 0:
+        if t > 0:
+            raise ValueError("training_pairs: an id of modulewise_true_edges is outside [0, N = 0)")
+        return torch.empty((2, 0), dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.bool, device=dev)
+    graph, y, info = _tp_launch(knn_idx.detach().contiguous(), mte.contiguous(),
+                                signal_mask.contiguous().view(torch.uint8), pid.contiguous(), _TP_MODES[mode])
+    return graph, y
+
+
+def _tp_launch(idx, mte, sm8, pid, mode, check=True):
+    """hgnn_training_pairs_count, the one host read, hgnn_training_pairs_fill on checked, contiguous device tensors:
+    (graph, y, info).  ``check=False`` (tests): a bad-id status fills all the same -- the kernels skip such an id."""
+    dev = idx.device
+    n, k, t = int(idx.shape[0]), int(idx.shape[1]), int(mte.shape[1])
+    lib = _lib.load()
+    ws, nb = _lib.workspace("hgnn_training_pairs_workspace_bytes", dev, n, k, t, mode)
+    info = torch.empty(_lib.TP_INFO, dtype=torch.int64, device=dev)
+    args = (_lib.ptr(idx), n, k, _lib.ptr(mte), t, _lib.ptr(sm8), _lib.ptr(pid), mode)
+    with torch.cuda.device(dev):
+        _lib.check(lib.hgnn_training_pairs_count(*args, _lib.ptr(info), _lib.ptr(ws), nb, _lib.current_stream(dev)),
+                   "hgnn_training_pairs_count")
+        stats["host_reads"] += 1
+        info = info.tolist()
+        p, status = info[_lib.TP_P], info[_lib.TP_STATUS]
+        if check and status & _lib.TP_ST_BAD_IDX:
+            raise ValueError(f"training_pairs: an entry of knn_idx is outside [-1, N = {n})")
+        if check and status & _lib.TP_ST_BAD_MTE:
+            raise ValueError(f"training_pairs: an id of modulewise_true_edges is outside [0, N = {n})")
+        graph = torch.empty((2, p), dtype=torch.int64, device=dev)
+        y = torch.empty(p, dtype=torch.uint8, device=dev)
+        _lib.check(lib.hgnn_training_pairs_fill(*args, _lib.ptr(graph), _lib.ptr(y), p, _lib.ptr(ws), nb,
+                                                _lib.current_stream(dev)),
+                   "hgnn_training_pairs_fill")
+    return graph, y.view(torch.bool), info
+
+
+def training_samples(embeddings, batch, hparams, prediction_graph=None, fused=False):
     """EmbeddingBase.get_training_samples (embedding_base.py:109-135) for both ``true_edges`` modes.  ``batch``:
     anything with ``modulewise_true_edges``, ``signal_mask`` and ``pid`` (attributes or keys) on the embeddings'
     device.  ``prediction_graph`` replaces the kNN graph when given (the reference always builds it); the optional
-    ``hparams["knn_method"]`` is frnn_graph's ``method``."""
+    ``hparams["knn_method"]`` is frnn_graph's ``method``.  ``fused=True``: the same result, bit for bit, from
+    ``knn_radius`` and ``training_pairs`` -- one host read, no prediction graph (so none can be given)."""
+    if fused:
+        if prediction_graph is not None:
+            raise ValueError("training_samples(fused=True) builds the pairs from the kNN matrix: it takes no "
+                             "prediction_graph")
+        if not torch.is_tensor(embeddings) or not embeddings.is_cuda:
+            raise RuntimeError("training_samples(fused=True) needs HIP device tensors: hierarchicalgnn_amd has no "
+                               "CPU path")
+        method = _knn_method(hparams)
+        idx = knn_radius(embeddings, embeddings, int(hparams["knn"]), hparams["train_r"],
+                         method=FRNN_DEFAULT_METHOD if method is None else method)
+        return training_pairs(idx, batch, hparams)
     dev = embeddings.device
     if prediction_graph is None:
         prediction_graph = frnn_graph(embeddings, hparams["train_r"], hparams["knn"], _knn_method(hparams))
@@ -302,24 +401,25 @@ def pair_hinge_loss(embeddings, graph, y, batch, hparams, margin=None, scale=1.0
     return loss
 
 
-def embedding_in_training_loss(embeddings, batch, hparams, prediction_graph=None):
-    """EmbeddingBase.training_step for Embedding-IN after the forward (embedding_base.py:191-199)"""
-    graph, y = training_samples(embeddings, batch, hparams, prediction_graph)
+def embedding_in_training_loss(embeddings, batch, hparams, prediction_graph=None, fused_samples=False):
+    """EmbeddingBase.training_step for Embedding-IN after the forward (embedding_base.py:191-199);
+    ``fused_samples``: training_samples' ``fused``"""
+    graph, y = training_samples(embeddings, batch, hparams, prediction_graph, fused=fused_samples)
     return pair_hinge_loss(embeddings, graph, y, batch, hparams)
 
 
 def embedding_hgnn_training_loss(embeddings, intermediate_embeddings, batch, hparams, loss_schedule,
-                                 prediction_graph=None):
+                                 prediction_graph=None, fused_samples=False):
     """EmbeddingBase.training_step for Embedding-HGNN-GMM after the forward (embedding_base.py:160-181):
     (loss, emb_loss, intermediate_loss) with loss = loss_schedule * intermediate_loss + (1 - loss_schedule) * emb_loss.
     The intermediate term is the PID truth on ``batch.edge_index`` with the intermediate embeddings, the second term
     ``training_samples`` with the final ones.  ``loss_schedule`` is the caller's (the reference takes it from hparams
-    or from the epoch, :177-180)."""
+    or from the epoch, :177-180).  ``fused_samples``: training_samples' ``fused``."""
     edge_index = _field(batch, "edge_index")
     pid = _field(batch, "pid")
     y_pid = pid[edge_index[0]] == pid[edge_index[1]]
     intermediate_loss = pair_hinge_loss(intermediate_embeddings, edge_index, y_pid, batch, hparams, cache_plan=True)
-    graph, y = training_samples(embeddings, batch, hparams, prediction_graph)
+    graph, y = training_samples(embeddings, batch, hparams, prediction_graph, fused=fused_samples)
     emb_loss = pair_hinge_loss(embeddings, graph, y, batch, hparams)
     loss = (loss_schedule * intermediate_loss) + ((1 - loss_schedule) * emb_loss)
     return loss, emb_loss, intermediate_loss

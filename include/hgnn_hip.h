@@ -54,7 +54,8 @@ extern "C" {
  * no existing entry point, struct or constant changed layout or meaning.  The same holds for
  * hgnn_segment_reduce_f32_ex, hgnn_plan_item_order(_workspace_bytes), hgnn_get_option and the optimiser step
  * (hgnn_optim_*, hgnn_sizeof_opt_entry, struct hgnn_opt_entry, HGNN_OPT_*), for hgnn_wgrad_f32(_workspace_bytes) and for
- * hgnn_track_records(_workspace_bytes) with struct hgnn_tr_particles, struct hgnn_tr_candidates and HGNN_TR_*. */
+ * hgnn_track_records(_workspace_bytes) with struct hgnn_tr_particles, struct hgnn_tr_candidates and HGNN_TR_*, and
+ * for hgnn_training_pairs_workspace_bytes, hgnn_training_pairs_count and hgnn_training_pairs_fill with HGNN_TP_*. */
 #define HGNN_ABI_VERSION 26
 
 typedef void* hgnn_stream_t; /* hipStream_t */
@@ -1191,6 +1192,46 @@ int hgnn_event_edges_fill(const int64_t* edges, int64_t E, const uint8_t* edge_k
                           uint8_t* y_pid_out, const void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
 int hgnn_event_gather_rows(const void* src, int64_t n_rows, int32_t cols, int32_t elem_bytes, const int64_t* index,
                            int64_t n_out, void* out, hgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Training pairs of the embedding stage (reference GNNEmbedding/embedding_base.py:109-135, get_training_samples)
+ * from the kNN matrix, row by row: no [2, N*K] prediction graph and no sort of the pairs (csrc/trainpairs.hip).
+ * Added under ABI 26: additions only.  Every entry launches on `stream`, allocates nothing, never synchronises and
+ * reads nothing back (the size query needs the HIP runtime and a device for rocprim's scratch sizes; its argument
+ * checks come first).  No atomic decides a position: the output is a deterministic function of the inputs.
+ *
+ * idx int64 [n, K], 1 <= K <= HGNN_TP_MAX_K: ids in [0, n), -1 = empty slot (anywhere in a row), duplicates allowed.
+ * mte int64 [2, t]; signal_mask one byte per hit [n]; pid int64 [n].  n < 2^31, t < 2^29 and n K + 2 t < 2^31, else
+ * HGNN_ERR_INVALID_ARG.  e_bidir = the columns of [mte, mte.flip(0)] whose two ends pass signal_mask, in that order.
+ *   HGNN_TP_MODE_MODULEWISE: for row i ascending, its DISTINCT valid ids j ascending with (i, j) not in e_bidir and
+ *     (pid[i] != pid[j] || pid[i] == 0 || pid[j] == 0), y = 0; then all of e_bidir, y = 1.
+ *   HGNN_TP_MODE_PID: for row i ascending, every valid slot j in slot order with !(signal_mask[i] && signal_mask[j])
+ *     and !(pid[i] == pid[j] && pid[i] != 0 && pid[j] != 0), y = 0; nothing of e_bidir (its pairs pass the mask).
+ * hgnn_training_pairs_count: info device int64[HGNN_TP_INFO] = {P, the pairs of the row part, the pairs of the
+ *   e_bidir part, status}.  status: HGNN_TP_ST_BAD_IDX when an entry of idx is outside [-1, n), HGNN_TP_ST_BAD_MTE
+ *   when an id of mte is outside [0, n) (checked in both modes); such a slot or column is skipped and the id never
+ *   used as an address.  The sorted e_bidir keys and the scanned positions stay in the workspace for
+ * hgnn_training_pairs_fill, which must be given the same workspace, untouched, and the same inputs: out_graph int64
+ *   [2, cap] and out_y uint8 [cap] receive every pair whose position is < cap (cap = P: exactly the result).
+ * ------------------------------------------------------------------------ */
+#define HGNN_TP_MAX_K 128
+#define HGNN_TP_MODE_MODULEWISE 0
+#define HGNN_TP_MODE_PID 1
+#define HGNN_TP_ST_BAD_IDX 1
+#define HGNN_TP_ST_BAD_MTE 2
+#define HGNN_TP_P 0
+#define HGNN_TP_N_ROW 1
+#define HGNN_TP_N_TRUTH 2
+#define HGNN_TP_STATUS 3
+#define HGNN_TP_INFO 4
+int hgnn_training_pairs_workspace_bytes(int64_t n, int32_t K, int64_t t, int32_t mode, size_t* bytes);
+int hgnn_training_pairs_count(const int64_t* idx, int64_t n, int32_t K, const int64_t* mte, int64_t t,
+                              const uint8_t* signal_mask, const int64_t* pid, int32_t mode, int64_t* info,
+                              void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
+int hgnn_training_pairs_fill(const int64_t* idx, int64_t n, int32_t K, const int64_t* mte, int64_t t,
+                             const uint8_t* signal_mask, const int64_t* pid, int32_t mode, int64_t* out_graph,
+                             uint8_t* out_y, int64_t cap, const void* workspace, size_t workspace_bytes,
+                             hgnn_stream_t stream);
 
 #ifdef __cplusplus
 }
