@@ -9,6 +9,9 @@ Drop-in surface (same names / signatures as the reference):
     eval_metrics(bipartite_graph, event, ...)            <- Modules/tracking_utils.py
     track_records(bipartite_graph, event, bins, ...)     eval_metrics plus per-particle / per-candidate tables and
                                                          binned counts (no counterpart in the reference)
+    edge_score_scan(...), bipartite_score_scan(...), ec_score_scan(...), bc_score_scan(...)
+                                                         the tracking metrics at every score cut of a list in one
+                                                         device call (the reference evaluates one hard-coded cut)
     graph_intersection(...), frnn_graph(...)             <- Modules/utils.py (embedding stage)
     training_samples(...), training_pairs(knn_idx, ...)  <- EmbeddingBase.get_training_samples (the second: from the kNN matrix)
     bipartite_loss(...), bc_training_loss(...)           <- BipartiteClassificationBase.get_bipartite_loss / training_step
@@ -30,6 +33,7 @@ from .utils import make_mlp  # noqa: F401
 from .gnn_utils import InteractionGNNCell, HierarchicalGNNCell  # noqa: F401
 from .tracking import eval_metrics, edge_track_candidates, bipartite_track_candidates  # noqa: F401
 from .tracking import embedding_track_candidates, track_records  # noqa: F401
+from .tracking import edge_score_scan, bipartite_score_scan  # noqa: F401
 from .hdbscan import hdbscan, hdbscan_tree  # noqa: F401  (the name `hdbscan` is the function; the module is
 #                                             importlib.import_module("hierarchicalgnn_amd.hdbscan"))
 from .embedding import frnn_graph, graph_intersection, training_samples, training_weights, hinge_distance  # noqa: F401
@@ -37,9 +41,9 @@ from .embedding import training_pairs  # noqa: F401
 from .embedding import (pair_hinge_loss, pair_hinge_check, embedding_hgnn_training_loss,  # noqa: F401
                         embedding_in_training_loss)
 from .assignment import (max_weight_matching, bipartite_loss, bc_embedding_loss, bc_training_loss,  # noqa: F401
-                         gap_bound)
+                         gap_bound, bc_score_scan)
 from .edge_classifier import (weighted_bce_loss, weighted_bce_check, ec_training_loss,  # noqa: F401
-                              ec_shared_evaluation)
+                              ec_shared_evaluation, ec_score_scan)
 from .optim import FusedAdamW, configure_optimizers, optimizer_step  # noqa: F401
 from .ops import knn_edges  # noqa: F401
 from .graph_construction import attention_weights  # noqa: F401

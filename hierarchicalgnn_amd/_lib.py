@@ -30,6 +30,12 @@ DT_F32, DT_BF16, DT_I32, DT_I64, DT_F64 = 0, 1, 2, 3, 4   # HGNN_DT_*
  TE_NO_MATCH, TE_STATUS, TE_N_MATCH, TE_RESULT) = range(13)
 # HGNN_TR_*: hgnn_track_records' limits and histogram columns
 TR_MAX_VARS, TR_MAX_BINS, TR_COLUMNS = 4, 64, 6
+# HGNN_TS_*: hgnn_track_scan's modes, limit, the three item counts after the HGNN_TE_* entries of a row, and the
+# reserved candidate label
+TS_EDGE, TS_PAIR = 0, 1
+TS_MAX_CUTS = 64
+TS_N_PASS, TS_N_TRUE_PASS, TS_N_TRUE, TS_ROW = 12, 13, 14, 15
+TS_RESERVED_LABEL = 2 ** 63 - 1
 
 # HGNN_AM_*: hgnn_assign_match's constants, status bits and the entries of its info vector
 AM_SCALE_BITS, AM_FALLBACK_WEIGHT = 30, 1e-12
@@ -232,6 +238,10 @@ _SIGNATURES = {
                                    c_int32, POINTER(c_float), POINTER(c_int32), c_double, c_double, c_double,
                                    c_void_p, POINTER(HgnnTrParticles), POINTER(HgnnTrCandidates), c_void_p, c_void_p,
                                    c_size_t, c_void_p]),
+    "hgnn_track_scan_workspace_bytes": (c_int, [c_int32, c_int64, c_int64, c_int64, c_int32, POINTER(c_size_t)]),
+    "hgnn_track_scan": (c_int, [c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_int64,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double,
+                                c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "hgnn_graph_intersection_workspace_bytes": (c_int, [c_int64, c_int64, c_int32, POINTER(c_size_t)]),
     "hgnn_graph_intersection": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

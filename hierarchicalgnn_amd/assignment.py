@@ -12,6 +12,9 @@ scores go to the host, scipy builds a CSR matrix (summing the scores of each (pa
     bc_embedding_loss(embeddings, edge_index, batch, hparams)               training_step :199-204
     bc_training_loss(bipartite_graph, bipartite_scores, embeddings, batch, hparams, loss_schedule)
                                                            training_step :196-213 after the forward
+    bc_score_scan(bipartite_graph, bipartite_scores, batch, event, hparams, cuts)
+                                                           the tracking metrics of shared_evaluation (:262-276) at every
+                                                           score cut of a list: tracking.bipartite_score_scan
 
 One stated difference from the reference: a pair's weight is the float64 sum of its float32 scores in position order
 (scipy sums float32 in CSR order).  On scores that are multiples of 2^-12 both are exact and equal.  Weights that
@@ -236,3 +239,16 @@ def bc_training_loss(bipartite_graph, bipartite_scores, embeddings, batch, hpara
     asgmt_loss = bipartite_loss(bipartite_scores, bipartite_graph, batch, hparams, fused=fused)
     loss = (loss_schedule * emb_loss) + ((1 - loss_schedule) * asgmt_loss)
     return loss, emb_loss, asgmt_loss
+
+
+def bc_score_scan(bipartite_graph, bipartite_scores, batch, event, hparams, cuts):
+    """The tracking metrics of BC-HGNN-GMM's and gMRT's shared_evaluation (bipartite_classification_base.py:262-276,
+    gmrt_base.py:269) at every score cut of ``cuts`` instead of at ``hparams["score_cut"]``
+    (``tracking.bipartite_score_scan``: one device call, ONE host read).  ``batch`` carries ``inverse_mask``;
+    ``event.pt`` is zeroed at ``pid == 0`` on a copy; ``hparams`` carries ptcut, n_hits and majority_cut."""
+    from .tracking import bipartite_score_scan
+    pid, pt = _field(event, "pid"), _field(event, "pt")
+    ev = {"pid": pid, "pt": torch.where(pid == 0, torch.zeros_like(pt), pt)}
+    return bipartite_score_scan(bipartite_graph, bipartite_scores, cuts, _field(batch, "inverse_mask"), ev,
+                                pt_cut=hparams["ptcut"], nhits_cut=hparams["n_hits"],
+                                majority_cut=hparams["majority_cut"], primary=False)

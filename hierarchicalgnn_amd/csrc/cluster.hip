@@ -18,6 +18,7 @@
 // Every loop a wave runs here has a strictly decreasing quantity (vertex id while climbing to a root,
 // candidate root id after a failed CAS), so the grid always drains.
 #include "common.h"
+#include "unionfind.h"
 
 namespace hgnn {
 
@@ -249,26 +250,7 @@ __global__ void k_gmm_cut(double* state, float granularity, int training, float 
 }
 
 // ------------------------------------------------------------------------------------------- components
-// parent[] is read and written by every workgroup while links are made by atomicCAS: relaxed agent-scope
-// atomics keep the compiler from caching entries in registers and the loads out of the per-CU vector cache.
-// A stale value would still be harmless (links are never removed and every link is validated by its CAS).
-__device__ __forceinline__ int ld_parent(const int* parent, int v) {
-    return __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int uf_find(int* parent, int v) {
-    // climb to the root; parents always have SMALLER ids, so the walk is finite.  Path halving writes are
-    // benign races: they only ever replace the parent of a NON-root by one of its ancestors.
-    int p = ld_parent(parent, v);
-    while (p != v) {
-        const int gp = ld_parent(parent, p);
-        if (gp != p) __hip_atomic_store(parent + v, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        v = p;
-        p = gp;
-    }
-    return v;
-}
-
+// the union-find itself (ld_parent, uf_find, uf_union, uf_compress) is in unionfind.h, shared with trackscan.hip
 __global__ __launch_bounds__(256) void k_cc_init(int* __restrict__ parent, int* __restrict__ present, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) {
@@ -288,29 +270,13 @@ __global__ __launch_bounds__(256) void k_cc_hook(const int64_t* __restrict__ src
     if (u64 < 0 || v64 < 0 || u64 >= n || v64 >= n) return;
     present[u64] = 1;
     present[v64] = 1;
-    int a = uf_find(parent, (int)u64);
-    int b = uf_find(parent, (int)v64);
-    while (a != b) {
-        const int hi = a > b ? a : b, lo = a > b ? b : a;
-        const int old = atomicCAS(&parent[hi], hi, lo);
-        if (old == hi) break;  // hi was still a root: now it hangs under lo
-        // hi had been linked under `old` (< hi) meanwhile: continue from there; max(a, b) strictly decreases
-        a = uf_find(parent, old);
-        b = lo;
-    }
+    uf_union(parent, (int)u64, (int)v64);
 }
 
 __global__ __launch_bounds__(256) void k_cc_compress(int* parent, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    int r = (int)i;
-    int p = ld_parent(parent, r);
-    while (p != r) {  // no more links are made: a read-only climb over strictly decreasing ids
-        r = p;
-        p = ld_parent(parent, r);
-    }
-    // races with other climbers only replace a parent by its root
-    __hip_atomic_store(parent + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uf_compress(parent, (int)i);
 }
 
 }  // namespace hgnn

@@ -34,7 +34,9 @@
 // The two means are sums in a fixed order (lanes, wave butterfly, blocks of
 // particles, one final block), so two calls give the same bits.
 //
-// The kernels and the workspace layout are in trackeval_common.h, shared with
+// The kernels, the workspace layout and the launch sequence (in stages) are in
+// trackeval_common.h, shared with hgnn_track_scan (trackscan.hip), which runs the
+// particle stage once for many pair sets of one event, and with
 // hgnn_track_records (trackeval_records.hip), which runs the same pipeline and
 // keeps the per-particle and per-candidate results.  This file instantiates
 // k_te_match<false>: no store beyond the per-particle sums and counts.
@@ -71,83 +73,39 @@ extern "C" int hgnn_track_eval(const int64_t* hit, const int64_t* cand, int64_t 
     rc = te_layout(n_pairs, n_hits, &w, stream);
     if (rc != HGNN_OK) return rc;
     HGNN_REQUIRE_WORKSPACE("hgnn_track_eval", workspace, workspace_bytes, w.total);
-    char* ws = (char*)workspace;
-    auto I32 = [&](size_t o) { return (int32_t*)(ws + o); };
+    const TePtrs p = te_ptrs(workspace, w);
     const int B = (int)n_pairs, N = (int)n_hits;
-    const int cbits = bit_width(B), pbits = bit_width(N);
-    void* temp = ws + w.temp;
-    size_t tb = w.temp_bytes;
+    size_t tb = p.temp_bytes;
 
     if (B > 0) {
-        int32_t *cv_in = I32(w.cv_in), *cv = I32(w.cv), *cflag = I32(w.cflag), *crid = I32(w.crid);
-        int32_t *cstart = I32(w.cstart), *ckeep = I32(w.ckeep), *kscan = I32(w.kscan), *ccol = I32(w.ccol);
-        int64_t* ck = (int64_t*)(ws + w.ck);
-        uint64_t *key = (uint64_t*)(ws + w.key), *skey = (uint64_t*)(ws + w.skey);
-        int32_t *tflag = I32(w.tflag), *trid = I32(w.trid), *tstart = I32(w.tstart);
-        int32_t *pv_in = I32(w.pv_in), *pv = I32(w.pv), *pflag = I32(w.pflag), *prid = I32(w.prid);
-        int32_t *pstart = I32(w.pstart), *hit_p = I32(w.hit_p), *nhits = I32(w.nhits), *prim = I32(w.prim);
-        int32_t *prow_b = I32(w.prow_b), *prow_e = I32(w.prow_e), *err = I32(w.err);
-        int64_t *pk = (int64_t*)(ws + w.pk), *opid = (int64_t*)(ws + w.opid);
-        float* ptmin = (float*)(ws + w.ptmin);
-        double* pp_sum = (double*)(ws + w.pp_sum);
-        int4* pp_cnt = (int4*)(ws + w.pp_cnt);
-        const uint64_t sentinel = (uint64_t)N << cbits;
-
-        HGNN_CHECK_HIP(hipMemsetAsync(err, 0, sizeof(int32_t), stream));
-        HGNN_CHECK_HIP(hipMemsetAsync(prow_b, 0, (size_t)N * 4, stream));
-        HGNN_CHECK_HIP(hipMemsetAsync(prow_e, 0, (size_t)N * 4, stream));
-
+        rc = te_clear(p, N, stream);
+        if (rc != HGNN_OK) return rc;
         // step 1: candidate runs, size filter, dense relabel
-        k_te_iota<<<blocks_for(B), 256, 0, stream>>>(cv_in, B);
-        HGNN_CHECK_HIP(rocprim::radix_sort_pairs(temp, tb, cand, ck, cv_in, cv, (size_t)B, 0u, 64u, stream));
-        k_te_heads<int64_t, false><<<blocks_for(B), 256, 0, stream>>>(ck, B, 0, cflag);
-        HGNN_CHECK_HIP(rocprim::inclusive_scan(temp, tb, cflag, crid, (size_t)B, rocprim::plus<int32_t>(), stream));
-        k_te_starts<int64_t, false><<<blocks_for(B), 256, 0, stream>>>(ck, cflag, crid, B, 0, cstart);
+        rc = te_candidate_runs(p, cand, B, stream);
+        if (rc != HGNN_OK) return rc;
         const float thr = (float)(nhits_cut * majority_cut);
-        k_te_cand_keep<<<blocks_for(B), 256, 0, stream>>>(cstart, crid, B, thr, ckeep);
-        HGNN_CHECK_HIP(rocprim::inclusive_scan(temp, tb, ckeep, kscan, (size_t)B, rocprim::plus<int32_t>(), stream));
-
+        k_te_cand_keep<<<blocks_for(B), 256, 0, stream>>>(p.cstart, p.crid, B, thr, p.ckeep);
+        rc = te_candidate_relabel(p, B, stream);
+        if (rc != HGNN_OK) return rc;
         // step 2: particles
-        k_te_iota<<<blocks_for(N), 256, 0, stream>>>(pv_in, N);
-        HGNN_CHECK_HIP(rocprim::radix_sort_pairs(temp, tb, pid, pk, pv_in, pv, (size_t)N, 0u, 64u, stream));
-        k_te_heads<int64_t, false><<<blocks_for(N), 256, 0, stream>>>(pk, N, 0, pflag);
-        HGNN_CHECK_HIP(rocprim::inclusive_scan(temp, tb, pflag, prid, (size_t)N, rocprim::plus<int32_t>(), stream));
-        k_te_starts<int64_t, false><<<blocks_for(N), 256, 0, stream>>>(pk, pflag, prid, N, 0, pstart);
-        k_te_hit_particle<<<blocks_for(N), 256, 0, stream>>>(pv, prid, N, hit_p);
-        k_te_particles<<<wave_blocks(N), 256, 0, stream>>>(pstart, prid, pv, pk, pt, primary, N, nhits, opid, ptmin,
-                                                           prim);
-
-        // step 3: contingency triples (p, c, n), row-major
-        k_te_pair_keys<<<blocks_for(B), 256, 0, stream>>>(cv, crid, cstart, ckeep, kscan, hit, hit_p, B, N, cbits,
-                                                          key, ccol, err);
-        HGNN_CHECK_HIP(rocprim::radix_sort_keys(temp, tb, key, skey, (size_t)B, 0u, (unsigned)(pbits + cbits),
-                                                stream));
-        k_te_heads<uint64_t, true><<<blocks_for(B), 256, 0, stream>>>(skey, B, sentinel, tflag);
-        HGNN_CHECK_HIP(rocprim::inclusive_scan(temp, tb, tflag, trid, (size_t)B, rocprim::plus<int32_t>(), stream));
-        k_te_starts<uint64_t, true><<<blocks_for(B), 256, 0, stream>>>(skey, tflag, trid, B, sentinel, tstart);
-        k_te_rows<<<blocks_for(B), 256, 0, stream>>>(skey, tstart, trid, B, cbits, prow_b, prow_e);
-
-        // steps 4-7
+        rc = te_particle_stage(p, pid, pt, primary, N, stream);
+        if (rc != HGNN_OK) return rc;
+        // step 3: contingency triples (p, c, n), row-major; steps 4-7
         TeParams prm{majority_cut, nhits_cut, majority_cut * nhits_cut, (float)pt_cut, primary != nullptr ? 1 : 0};
-        k_te_match<false><<<wave_blocks(N), 256, 0, stream>>>(prow_b, prow_e, skey, tstart, ccol, kscan, prid, nhits,
-                                                              opid, ptmin, prim, B, N, cbits, prm, pp_sum, pp_cnt,
-                                                              TeMatchRecords<false>{});
-        k_te_reduce<<<kRedBlocks, 256, 0, stream>>>(pp_sum, pp_cnt, prid, N, (double*)(ws + w.blk_sum),
-                                                    (long long*)(ws + w.blk_cnt));
-        k_te_finalize<<<1, kRedBlocks, 0, stream>>>((double*)(ws + w.blk_sum), (long long*)(ws + w.blk_cnt), prid,
-                                                    kscan, B, N, err, result);
+        rc = te_match_stage(p, hit, B, N, prm, stream);
+        if (rc != HGNN_OK) return rc;
+        k_te_finalize<<<1, kRedBlocks, 0, stream>>>(p.blk_sum, p.blk_cnt, p.prid, p.kscan, B, N, p.err, result);
     } else {
         // no pairs: default response; P is still counted when the event has hits
-        int32_t *pv_in = I32(w.pv_in), *pv = I32(w.pv), *pflag = I32(w.pflag), *prid = I32(w.prid);
-        int64_t* pk = (int64_t*)(ws + w.pk);
         if (N > 0) {
-            k_te_iota<<<blocks_for(N), 256, 0, stream>>>(pv_in, N);
-            HGNN_CHECK_HIP(rocprim::radix_sort_pairs(temp, tb, pid, pk, pv_in, pv, (size_t)N, 0u, 64u, stream));
-            k_te_heads<int64_t, false><<<blocks_for(N), 256, 0, stream>>>(pk, N, 0, pflag);
-            HGNN_CHECK_HIP(rocprim::inclusive_scan(temp, tb, pflag, prid, (size_t)N, rocprim::plus<int32_t>(),
+            k_te_iota<<<blocks_for(N), 256, 0, stream>>>(p.pv_in, N);
+            HGNN_CHECK_HIP(rocprim::radix_sort_pairs(p.temp, tb, pid, p.pk, p.pv_in, p.pv, (size_t)N, 0u, 64u,
+                                                     stream));
+            k_te_heads<int64_t, false><<<blocks_for(N), 256, 0, stream>>>(p.pk, N, 0, p.pflag);
+            HGNN_CHECK_HIP(rocprim::inclusive_scan(p.temp, tb, p.pflag, p.prid, (size_t)N, rocprim::plus<int32_t>(),
                                                    stream));
         }
-        k_te_finalize<<<1, kRedBlocks, 0, stream>>>(nullptr, nullptr, prid, nullptr, 0, N, nullptr, result);
+        k_te_finalize<<<1, kRedBlocks, 0, stream>>>(nullptr, nullptr, p.prid, nullptr, 0, N, nullptr, result);
     }
     HGNN_CHECK_HIP(hipGetLastError());
     return HGNN_OK;

@@ -392,17 +392,14 @@ __global__ __launch_bounds__(256) void k_te_reduce(const double* __restrict__ pp
     }
 }
 
-// second level (one block of kRedBlocks threads) and the metrics
-__global__ __launch_bounds__(kRedBlocks) void k_te_finalize(const double* __restrict__ blk_sum,
-                                                            const long long* __restrict__ blk_cnt,
-                                                            const int32_t* __restrict__ prid,
-                                                            const int32_t* __restrict__ kscan, int B, int N,
-                                                            const int32_t* __restrict__ err,
-                                                            double* __restrict__ result) {
+// second level (one block of kRedBlocks threads) and the metrics.  run: the pipeline ran (there were pairs and hits);
+// without it the row is the default response with P still counted.  status: what HGNN_TE_STATUS receives
+__device__ inline void te_finalize_row(const double* __restrict__ blk_sum, const long long* __restrict__ blk_cnt,
+                                       const int32_t* __restrict__ prid, const int32_t* __restrict__ kscan, int B, int N,
+                                       bool run, double status, double* __restrict__ result) {
     __shared__ double s_sum[2][kRedBlocks];
     __shared__ long long s_cnt[4][kRedBlocks];
     const int tid = threadIdx.x;
-    const bool run = B > 0 && N > 0;
     for (int k = 0; k < 2; ++k) s_sum[k][tid] = run ? blk_sum[2 * tid + k] : 0.0;
     for (int k = 0; k < 4; ++k) s_cnt[k][tid] = run ? blk_cnt[4 * tid + k] : 0;
     __syncthreads();
@@ -428,8 +425,18 @@ __global__ __launch_bounds__(kRedBlocks) void k_te_finalize(const double* __rest
     result[HGNN_TE_N_CAND] = (double)C;
     result[HGNN_TE_N_PART] = (double)P;
     result[HGNN_TE_NO_MATCH] = (n_match == 0 || n_kept == 0) ? 1.0 : 0.0;
-    result[HGNN_TE_STATUS] = (run && *err != 0) ? 1.0 : 0.0;
+    result[HGNN_TE_STATUS] = status;
     result[HGNN_TE_N_MATCH] = (double)n_match;
+}
+
+__global__ __launch_bounds__(kRedBlocks) void k_te_finalize(const double* __restrict__ blk_sum,
+                                                            const long long* __restrict__ blk_cnt,
+                                                            const int32_t* __restrict__ prid,
+                                                            const int32_t* __restrict__ kscan, int B, int N,
+                                                            const int32_t* __restrict__ err,
+                                                            double* __restrict__ result) {
+    const bool run = B > 0 && N > 0;
+    te_finalize_row(blk_sum, blk_cnt, prid, kscan, B, N, run, (run && *err != 0) ? 1.0 : 0.0, result);
 }
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)ceil_div(n > 0 ? n : 1, 256); }
@@ -442,6 +449,109 @@ inline int te_check_sizes(const char* who, int64_t n_pairs, int64_t n_hits) {
     HGNN_REQUIRE(n_pairs >= 0 && n_hits >= 0, "%s: negative size", who);
     HGNN_REQUIRE(n_pairs < ((int64_t)1 << 31) - 1 && n_hits < ((int64_t)1 << 31) - 1,
                  "%s: more than 2^31 - 2 pairs or hits", who);
+    return HGNN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- launch sequences
+// The pipeline in stages, so that a caller that evaluates many pair sets of ONE event (trackscan.hip) runs the
+// particle stage once.  hgnn_track_eval is te_candidate_runs, k_te_cand_keep + te_candidate_relabel,
+// te_particle_stage, te_match_stage and k_te_finalize, in that order.
+struct TePtrs {
+    int32_t *cv_in, *cv, *cflag, *crid, *cstart, *ckeep, *kscan, *ccol;
+    int64_t* ck;
+    uint64_t *key, *skey;
+    int32_t *tflag, *trid, *tstart;
+    int32_t *pv_in, *pv, *pflag, *prid, *pstart, *hit_p, *nhits, *prim, *prow_b, *prow_e, *err;
+    int64_t *pk, *opid;
+    float* ptmin;
+    double *pp_sum, *blk_sum;
+    int4* pp_cnt;
+    long long* blk_cnt;
+    void* temp;
+    size_t temp_bytes;
+};
+
+inline TePtrs te_ptrs(void* workspace, const TeWorkspace& w) {
+    char* ws = (char*)workspace;
+    auto I32 = [&](size_t o) { return (int32_t*)(ws + o); };
+    TePtrs p;
+    p.cv_in = I32(w.cv_in), p.cv = I32(w.cv), p.cflag = I32(w.cflag), p.crid = I32(w.crid);
+    p.cstart = I32(w.cstart), p.ckeep = I32(w.ckeep), p.kscan = I32(w.kscan), p.ccol = I32(w.ccol);
+    p.ck = (int64_t*)(ws + w.ck);
+    p.key = (uint64_t*)(ws + w.key), p.skey = (uint64_t*)(ws + w.skey);
+    p.tflag = I32(w.tflag), p.trid = I32(w.trid), p.tstart = I32(w.tstart);
+    p.pv_in = I32(w.pv_in), p.pv = I32(w.pv), p.pflag = I32(w.pflag), p.prid = I32(w.prid);
+    p.pstart = I32(w.pstart), p.hit_p = I32(w.hit_p), p.nhits = I32(w.nhits), p.prim = I32(w.prim);
+    p.prow_b = I32(w.prow_b), p.prow_e = I32(w.prow_e), p.err = I32(w.err);
+    p.pk = (int64_t*)(ws + w.pk), p.opid = (int64_t*)(ws + w.opid);
+    p.ptmin = (float*)(ws + w.ptmin);
+    p.pp_sum = (double*)(ws + w.pp_sum), p.blk_sum = (double*)(ws + w.blk_sum);
+    p.pp_cnt = (int4*)(ws + w.pp_cnt);
+    p.blk_cnt = (long long*)(ws + w.blk_cnt);
+    p.temp = ws + w.temp;
+    p.temp_bytes = w.temp_bytes;
+    return p;
+}
+
+// the status word and the row ranges of one evaluation
+inline int te_clear(const TePtrs& p, int N, hipStream_t stream) {
+    HGNN_CHECK_HIP(hipMemsetAsync(p.err, 0, sizeof(int32_t), stream));
+    HGNN_CHECK_HIP(hipMemsetAsync(p.prow_b, 0, (size_t)N * 4, stream));
+    HGNN_CHECK_HIP(hipMemsetAsync(p.prow_e, 0, (size_t)N * 4, stream));
+    return HGNN_OK;
+}
+
+// step 1 up to the size filter: the runs of equal candidate labels (B > 0)
+inline int te_candidate_runs(const TePtrs& p, const int64_t* cand, int B, hipStream_t stream) {
+    size_t tb = p.temp_bytes;
+    k_te_iota<<<blocks_for(B), 256, 0, stream>>>(p.cv_in, B);
+    HGNN_CHECK_HIP(rocprim::radix_sort_pairs(p.temp, tb, cand, p.ck, p.cv_in, p.cv, (size_t)B, 0u, 64u, stream));
+    k_te_heads<int64_t, false><<<blocks_for(B), 256, 0, stream>>>(p.ck, B, 0, p.cflag);
+    HGNN_CHECK_HIP(rocprim::inclusive_scan(p.temp, tb, p.cflag, p.crid, (size_t)B, rocprim::plus<int32_t>(), stream));
+    k_te_starts<int64_t, false><<<blocks_for(B), 256, 0, stream>>>(p.ck, p.cflag, p.crid, B, 0, p.cstart);
+    return HGNN_OK;
+}
+
+// step 1 after the size filter: the dense label of every kept run
+inline int te_candidate_relabel(const TePtrs& p, int B, hipStream_t stream) {
+    size_t tb = p.temp_bytes;
+    HGNN_CHECK_HIP(rocprim::inclusive_scan(p.temp, tb, p.ckeep, p.kscan, (size_t)B, rocprim::plus<int32_t>(), stream));
+    return HGNN_OK;
+}
+
+// step 2: the particles (N > 0).  Nothing here depends on the pairs
+inline int te_particle_stage(const TePtrs& p, const int64_t* pid, const float* pt, const uint8_t* primary, int N,
+                             hipStream_t stream) {
+    size_t tb = p.temp_bytes;
+    k_te_iota<<<blocks_for(N), 256, 0, stream>>>(p.pv_in, N);
+    HGNN_CHECK_HIP(rocprim::radix_sort_pairs(p.temp, tb, pid, p.pk, p.pv_in, p.pv, (size_t)N, 0u, 64u, stream));
+    k_te_heads<int64_t, false><<<blocks_for(N), 256, 0, stream>>>(p.pk, N, 0, p.pflag);
+    HGNN_CHECK_HIP(rocprim::inclusive_scan(p.temp, tb, p.pflag, p.prid, (size_t)N, rocprim::plus<int32_t>(), stream));
+    k_te_starts<int64_t, false><<<blocks_for(N), 256, 0, stream>>>(p.pk, p.pflag, p.prid, N, 0, p.pstart);
+    k_te_hit_particle<<<blocks_for(N), 256, 0, stream>>>(p.pv, p.prid, N, p.hit_p);
+    k_te_particles<<<wave_blocks(N), 256, 0, stream>>>(p.pstart, p.prid, p.pv, p.pk, pt, primary, N, p.nhits, p.opid,
+                                                       p.ptmin, p.prim);
+    return HGNN_OK;
+}
+
+// steps 3-7 up to the first level of the reduction (B > 0, N > 0): contingency triples, matching, block sums
+inline int te_match_stage(const TePtrs& p, const int64_t* hit, int B, int N, const TeParams& prm,
+                          hipStream_t stream) {
+    size_t tb = p.temp_bytes;
+    const int cbits = bit_width(B), pbits = bit_width(N);
+    const uint64_t sentinel = (uint64_t)N << cbits;
+    k_te_pair_keys<<<blocks_for(B), 256, 0, stream>>>(p.cv, p.crid, p.cstart, p.ckeep, p.kscan, hit, p.hit_p, B, N,
+                                                      cbits, p.key, p.ccol, p.err);
+    HGNN_CHECK_HIP(rocprim::radix_sort_keys(p.temp, tb, p.key, p.skey, (size_t)B, 0u, (unsigned)(pbits + cbits),
+                                            stream));
+    k_te_heads<uint64_t, true><<<blocks_for(B), 256, 0, stream>>>(p.skey, B, sentinel, p.tflag);
+    HGNN_CHECK_HIP(rocprim::inclusive_scan(p.temp, tb, p.tflag, p.trid, (size_t)B, rocprim::plus<int32_t>(), stream));
+    k_te_starts<uint64_t, true><<<blocks_for(B), 256, 0, stream>>>(p.skey, p.tflag, p.trid, B, sentinel, p.tstart);
+    k_te_rows<<<blocks_for(B), 256, 0, stream>>>(p.skey, p.tstart, p.trid, B, cbits, p.prow_b, p.prow_e);
+    k_te_match<false><<<wave_blocks(N), 256, 0, stream>>>(p.prow_b, p.prow_e, p.skey, p.tstart, p.ccol, p.kscan,
+                                                          p.prid, p.nhits, p.opid, p.ptmin, p.prim, B, N, cbits, prm,
+                                                          p.pp_sum, p.pp_cnt, TeMatchRecords<false>{});
+    k_te_reduce<<<kRedBlocks, 256, 0, stream>>>(p.pp_sum, p.pp_cnt, p.prid, N, p.blk_sum, p.blk_cnt);
     return HGNN_OK;
 }
 

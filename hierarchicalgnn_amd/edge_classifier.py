@@ -14,6 +14,9 @@ same arithmetic with the max of the two endpoint weights and a second pT table. 
     ec_shared_evaluation(scores, batch, event, hparams)
                                                      shared_evaluation after the forward: (bipartite_graph, loss,
                                                      metrics) with tracking.edge_track_candidates and eval_metrics
+    ec_score_scan(scores, batch, event, hparams, cuts)
+                                                     the metrics of shared_evaluation at every score cut of a list, and
+                                                     the edge counts per cut: tracking.edge_score_scan
 
 One stated difference from the reference: a class of pairs without weight (an empty class in particular) contributes
 nothing where the reference's 0/0 makes the loss NaN.  There is no CPU path: inputs must be HIP device tensors.
@@ -147,24 +150,26 @@ def weighted_bce_loss(scores, graph, y, pt_a, hparams, pt_b=None, combine="sum",
     return loss
 
 
+def _ec_truth(who, batch, hparams):
+    """(y, keep or None) of the edge classifier's loss in the ``true_edges`` mode of ``hparams``"""
+    mode = hparams["true_edges"]
+    if mode not in ("modulewise_true_edges", "pid_true_edges"):
+        raise ValueError(f"{who}: true_edges must be 'modulewise_true_edges' or 'pid_true_edges', "
+                         f"got {mode!r}")
+    if mode == "modulewise_true_edges":
+        y, y_pid = _field(batch, "y"), _field(batch, "y_pid")
+        return y.bool(), (y_pid == 0) | (y == 1)
+    return _field(batch, "y_pid").bool(), None
+
+
 def ec_training_loss(scores, batch, hparams):
     """EdgeClassifierBase.training_step after the forward (edge_classifier_base.py:115-128), and the loss of
     shared_evaluation (:143-154).  ``batch``: anything with ``edge_index``, ``y``, ``y_pid`` and ``pt`` (attributes or
     keys) on the scores' device.  With ``true_edges == "modulewise_true_edges"`` the neutral edges (PID-true but not
     modulewise) are dropped through a keep mask: no compaction, no host read."""
-    mode = hparams["true_edges"]
-    if mode not in ("modulewise_true_edges", "pid_true_edges"):
-        raise ValueError(f"ec_training_loss: true_edges must be 'modulewise_true_edges' or 'pid_true_edges', "
-                         f"got {mode!r}")
+    y, keep = _ec_truth("ec_training_loss", batch, hparams)
     if not torch.is_tensor(scores) or not scores.is_cuda:
         raise RuntimeError("ec_training_loss needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
-    keep = None
-    if mode == "modulewise_true_edges":
-        y, y_pid = _field(batch, "y"), _field(batch, "y_pid")
-        keep = (y_pid == 0) | (y == 1)
-        y = y.bool()
-    else:
-        y = _field(batch, "y_pid").bool()
     return weighted_bce_loss(scores, _field(batch, "edge_index"), y, _field(batch, "pt"), hparams, keep=keep)
 
 
@@ -182,3 +187,17 @@ def ec_shared_evaluation(scores, batch, event, hparams):
     metrics = eval_metrics(bipartite_graph, ev, pt_cut=hparams["ptcut"], nhits_cut=hparams["n_hits"],
                            majority_cut=hparams["majority_cut"], primary=False)
     return bipartite_graph, loss, metrics
+
+
+def ec_score_scan(scores, batch, event, hparams, cuts):
+    """The tracking metrics of ``ec_shared_evaluation`` at every score cut of ``cuts`` instead of at
+    ``hparams["score_cut"]``, with the edge counts per cut (``tracking.edge_score_scan``: one device call, ONE host
+    read).  Truth and keep are formed as ``ec_training_loss`` forms them in the ``true_edges`` mode of ``hparams``;
+    ``event.pt`` is zeroed at ``pid == 0`` on a copy; ``hparams`` carries ptcut, n_hits and majority_cut."""
+    from .tracking import edge_score_scan
+    y, keep = _ec_truth("ec_score_scan", batch, hparams)
+    pid, pt = _field(event, "pid"), _field(event, "pt")
+    ev = {"pid": pid, "pt": torch.where(pid == 0, torch.zeros_like(pt), pt)}
+    return edge_score_scan(_field(batch, "edge_index"), scores, cuts, _field(batch, "inverse_mask"), ev,
+                           pt_cut=hparams["ptcut"], nhits_cut=hparams["n_hits"], majority_cut=hparams["majority_cut"],
+                           primary=False, truth=y, keep=keep)

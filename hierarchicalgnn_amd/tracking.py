@@ -19,6 +19,12 @@ cugraph (EdgeClassifier/edge_classifier_base.py:157-168); neither exists on ROCm
     embedding_track_candidates(embeddings, inverse_mask, min_cluster_size)
                                                    embedding_base.py:267-272: HDBSCAN clusters of the embeddings
                                                    (hdbscan.py, csrc/hdbscan.hip), noise dropped
+    edge_score_scan(edge_index, scores, cuts, inverse_mask, event, ...)
+    bipartite_score_scan(bipartite_graph, scores, cuts, inverse_mask, event, ...)
+                                                   what edge_track_candidates / bipartite_track_candidates followed by
+                                                   eval_metrics give at every one of up to 64 score cuts, and the
+                                                   integer edge counts per cut: one call of ``hgnn_track_scan``
+                                                   (csrc/trackscan.hip) and ONE host read for the whole list
 
 There is no CPU path: every input must be a HIP device tensor.
 """
@@ -277,3 +283,110 @@ def embedding_track_candidates(embeddings: torch.Tensor, inverse_mask: torch.Ten
     if inverse_mask is not None:
         hits = inverse_mask.to(torch.int64)[hits]
     return torch.stack([hits, labels], dim=0)
+
+
+def _cuts_f32(who, cuts) -> torch.Tensor:
+    """the score cuts as a host float32 tensor, rounded once, checked after the rounding"""
+    c = torch.as_tensor(cuts)
+    if c.is_cuda:
+        raise ValueError(f"{who}: cuts must be host values (a sequence or a CPU tensor)")
+    c = c.detach().reshape(-1).to(torch.float64).to(torch.float32)
+    if not 1 <= c.numel() <= _lib.TS_MAX_CUTS:
+        raise ValueError(f"{who}: 1..{_lib.TS_MAX_CUTS} cuts expected, got {c.numel()}")
+    if bool(torch.isnan(c).any()):
+        raise ValueError(f"{who}: a cut is NaN")
+    return c
+
+
+def _item_bytes(who, t, name, n):
+    if not torch.is_tensor(t) or t.dtype not in (torch.bool, torch.uint8) or t.numel() != n:
+        raise ValueError(f"{who}: {name} must be bool or uint8 with one entry per item ({n})")
+    return t.reshape(-1).contiguous().view(torch.uint8)
+
+
+def _score_scan(who, mode, graph, scores, cuts, inverse_mask, event, pt_cut, nhits_cut, majority_cut, primary, truth,
+                keep):
+    # the host-side argument checks come first (they need no device), then the device refusals
+    c = _cuts_f32(who, cuts)
+    if not torch.is_tensor(graph) or graph.dim() != 2 or graph.shape[0] != 2:
+        raise ValueError(f"{who}: a [2, n] graph expected, got {tuple(getattr(graph, 'shape', ()))}")
+    n_items = int(graph.shape[1])
+    if not torch.is_tensor(scores) or scores.numel() != n_items:
+        raise ValueError(f"{who}: one score per item expected ({n_items})")
+    if keep is not None and truth is None:
+        raise ValueError(f"{who}: keep needs truth")
+    truth8 = None if truth is None else _item_bytes(who, truth, "truth", n_items)
+    keep8 = None if keep is None else _item_bytes(who, keep, "keep", n_items)
+    if mode == _lib.TS_EDGE and inverse_mask is None:
+        raise ValueError(f"{who}: inverse_mask is needed")
+    if not scores.is_cuda:
+        raise RuntimeError(f"{who} needs HIP device tensors: hierarchicalgnn_amd has no CPU path")
+    a, b, pid, pt, prim = _inputs(who, graph, event, majority_cut, primary)
+    dev = graph.device
+    mask = None if inverse_mask is None else inverse_mask.reshape(-1).to(torch.int64).contiguous()
+    others = [scores] + [t for t in (mask, truth8, keep8) if t is not None]
+    if any(t.device != dev for t in others):
+        raise RuntimeError(f"{who} needs HIP device tensors on one device: hierarchicalgnn_amd has no CPU path")
+    scores = scores.detach().reshape(-1).float().contiguous()
+    T, n_vertices, N = c.numel(), 0 if mask is None else mask.numel(), pid.numel()
+    lib = _lib.load()
+    ws, nb = _lib.workspace("hgnn_track_scan_workspace_bytes", dev, mode, n_items, n_vertices, N, T)
+    result = torch.empty((T, _lib.TS_ROW), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        cuts_dev = c.pin_memory().to(dev, non_blocking=True)
+        _lib.check(lib.hgnn_track_scan(mode, _lib.ptr(a), _lib.ptr(b), n_items, _lib.ptr(scores), _lib.ptr(cuts_dev),
+                                       T, _lib.ptr(mask), n_vertices, _lib.ptr(truth8), _lib.ptr(keep8), _lib.ptr(pid),
+                                       _lib.ptr(pt), _lib.ptr(prim) if prim is not None else None, N, float(pt_cut),
+                                       float(nhits_cut), float(majority_cut), _lib.ptr(result), _lib.ptr(ws), nb,
+                                       _lib.current_stream(dev)), "hgnn_track_scan")
+    # the one host read of the scan, made as read_result makes it
+    stats["host_reads"] += 1
+    sync_mode = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode(0)
+    try:
+        host = result.cpu()
+    finally:
+        torch.cuda.set_sync_debug_mode(sync_mode)
+    rows = host.tolist()
+    if any(r[_lib.TE_STATUS] == 2 for r in rows):
+        raise ValueError(f"{who}: a candidate label equals the reserved value {_lib.TS_RESERVED_LABEL}")
+    if any(r[_lib.TE_STATUS] != 0 for r in rows):
+        raise ValueError(f"{who}: a hit id (after inverse_mask) is outside [0, len(event.pid)), or a hit id is "
+                         "outside inverse_mask")
+    metrics = []
+    for r in rows:
+        if r[_lib.TE_NO_MATCH] != 0:
+            metrics.append(dict(default_response))
+        else:
+            metrics.append({"track_eff": r[_lib.TE_TRACK_EFF], "track_pur": r[_lib.TE_TRACK_PUR],
+                            "hit_eff": r[_lib.TE_HIT_EFF], "hit_pur": r[_lib.TE_HIT_PUR]})
+    edges = None
+    if truth8 is not None:
+        edges = {"pass": [int(r[_lib.TS_N_PASS]) for r in rows],
+                 "true_pass": [int(r[_lib.TS_N_TRUE_PASS]) for r in rows],
+                 "true": [int(r[_lib.TS_N_TRUE]) for r in rows]}
+    return {"cuts": c.tolist(), "metrics": metrics, "result": host[:, :_lib.TE_RESULT].clone(), "edges": edges}
+
+
+def edge_score_scan(edge_index, scores, cuts, inverse_mask, event, pt_cut=1., nhits_cut=5, majority_cut=0.5,
+                    primary=True, truth=None, keep=None):
+    """``eval_metrics(edge_track_candidates(edge_index, scores, cut, inverse_mask), event, ...)`` for every ``cut`` of
+    ``cuts`` (1..64 host numbers, any order, repeats allowed, rounded to float32 once, none NaN) from one call of
+    ``hgnn_track_scan`` and ONE host read: the union-find is carried from the highest cut to the lowest, the
+    particle side of the evaluation runs once.  ``truth`` / ``keep``: per-edge bool or uint8 device tensors.
+
+    Returns ``{"cuts": the float32-rounded cuts as Python floats, "metrics": per cut what eval_metrics returns,
+    "result": the host float64 [T, 12] block of HGNN_TE_* rows, "edges": {"pass", "true_pass", "true"} as int lists
+    (#{keep, score >= cut}, #{keep, truth, score >= cut}, #{keep, truth}; keep None = all), or None without
+    truth}``, every list in the caller's cut order."""
+    return _score_scan("edge_score_scan", _lib.TS_EDGE, edge_index, scores, cuts, inverse_mask, event, pt_cut,
+                       nhits_cut, majority_cut, primary, truth, keep)
+
+
+def bipartite_score_scan(bipartite_graph, scores, cuts, inverse_mask, event, pt_cut=1., nhits_cut=5, majority_cut=0.5,
+                         primary=True, truth=None, keep=None):
+    """``eval_metrics(bipartite_track_candidates(bipartite_graph, scores, cut, inverse_mask), event, ...)`` for every
+    ``cut`` of ``cuts``; arguments and return value as for ``edge_score_scan`` (``inverse_mask`` None: hit ids are
+    taken as they are).  The candidate label 2^63 - 1 is reserved: a passing pair that carries it raises."""
+    return _score_scan("bipartite_score_scan", _lib.TS_PAIR, bipartite_graph, scores, cuts, inverse_mask, event,
+                       pt_cut, nhits_cut, majority_cut, primary, truth, keep)

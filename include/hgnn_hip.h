@@ -55,7 +55,8 @@ extern "C" {
  * hgnn_segment_reduce_f32_ex, hgnn_plan_item_order(_workspace_bytes), hgnn_get_option and the optimiser step
  * (hgnn_optim_*, hgnn_sizeof_opt_entry, struct hgnn_opt_entry, HGNN_OPT_*), for hgnn_wgrad_f32(_workspace_bytes) and for
  * hgnn_track_records(_workspace_bytes) with struct hgnn_tr_particles, struct hgnn_tr_candidates and HGNN_TR_*, and
- * for hgnn_training_pairs_workspace_bytes, hgnn_training_pairs_count and hgnn_training_pairs_fill with HGNN_TP_*. */
+ * for hgnn_training_pairs_workspace_bytes, hgnn_training_pairs_count and hgnn_training_pairs_fill with HGNN_TP_*, and
+ * for hgnn_track_scan(_workspace_bytes) with HGNN_TS_*. */
 #define HGNN_ABI_VERSION 26
 
 typedef void* hgnn_stream_t; /* hipStream_t */
@@ -795,6 +796,43 @@ int hgnn_track_records(const int64_t* hit, const int64_t* cand, int64_t n_pairs,
                        const int32_t* n_bins, double pt_cut, double nhits_cut, double majority_cut, double* result,
                        const struct hgnn_tr_particles* particles, const struct hgnn_tr_candidates* candidates,
                        int64_t* hist, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
+
+/* hgnn_track_scan: the tracking metrics of ONE event at n_cuts score cuts, in one call.  Added under ABI 26: additions only.
+ *   mode HGNN_TS_EDGE: a = src, b = dst (int64 [n_items]) are the edges of a graph on n_vertices vertices; the
+ *   candidates at a cut are the weakly connected components of the edges with score >= cut, and the evaluated pairs
+ *   are (inverse_mask[v], smallest vertex id of v's component) over the vertices v that touch such an edge
+ *   (hgnn_cc_labels at that cut; an edge with a vertex id outside [0, n_vertices) is skipped).  When no edge passes a
+ *   cut, the components of all edges with a non-NaN score are taken instead (edge_classifier_base.py:157-168).
+ *   mode HGNN_TS_PAIR: a = hit, b = cand (int64 [n_items]); the evaluated pairs at a cut are those with
+ *   score >= cut, hit ids mapped through inverse_mask (int64 [n_vertices]) when it is not NULL; with a mask, a hit
+ *   id outside [0, n_vertices) of a passing pair sets the status.  The label HGNN_TS_RESERVED_LABEL is reserved.
+ *   Every comparison is score >= cut in float32: a NaN score passes no cut.
+ *   cuts: DEVICE float32 [n_cuts], 1 <= n_cuts <= HGNN_TS_MAX_CUTS, in any order, repeats allowed, none NaN (the
+ *   rows of a list with a NaN cut are unspecified; nothing faults).
+ *   result: device double [n_cuts][HGNN_TS_ROW], row t for cuts[t].  Entries 0 .. HGNN_TE_RESULT - 1 are bit for bit
+ *   what hgnn_track_eval writes for that pair set (a cut with no pair: its n_pairs == 0 row), with
+ *   result[HGNN_TE_STATUS] = 2 when a passing pair carries the reserved label (that row is meaningless).  With truth
+ *   (uint8 [n_items]) the last three entries count items, keep (uint8 [n_items], NULL = all) selecting them:
+ *   N_PASS = #{keep, score >= cut}, N_TRUE_PASS = #{keep, truth, score >= cut}, N_TRUE = #{keep, truth}; without
+ *   truth they are 0.  pid, pt, primary, n_hits, pt_cut, nhits_cut, majority_cut: as for hgnn_track_eval.
+ *   Integer counting and the fixed-order sums of hgnn_track_eval only: two calls give the same bits.  Allocates
+ *   nothing; launches on `stream`; reads nothing back.
+ * hgnn_track_scan_workspace_bytes: device scratch of one call (any 256-B aligned). */
+#define HGNN_TS_EDGE 0
+#define HGNN_TS_PAIR 1
+#define HGNN_TS_MAX_CUTS 64
+#define HGNN_TS_N_PASS 12
+#define HGNN_TS_N_TRUE_PASS 13
+#define HGNN_TS_N_TRUE 14
+#define HGNN_TS_ROW 15
+#define HGNN_TS_RESERVED_LABEL INT64_MAX
+int hgnn_track_scan_workspace_bytes(int32_t mode, int64_t n_items, int64_t n_vertices, int64_t n_hits, int32_t n_cuts,
+                                    size_t* bytes);
+int hgnn_track_scan(int32_t mode, const int64_t* a, const int64_t* b, int64_t n_items, const float* score,
+                    const float* cuts, int32_t n_cuts, const int64_t* inverse_mask, int64_t n_vertices,
+                    const uint8_t* truth, const uint8_t* keep, const int64_t* pid, const float* pt,
+                    const uint8_t* primary, int64_t n_hits, double pt_cut, double nhits_cut, double majority_cut,
+                    double* result, void* workspace, size_t workspace_bytes, hgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * graph_intersection of the embedding stage (reference Modules/utils.py:117-166, scipy CSR there).  ABI 26.
