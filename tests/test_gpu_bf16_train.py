@@ -64,7 +64,8 @@ def test_ln_act_bf16_row_kernels(W, act):
     assert rel_err(dz.float().cpu().numpy(), zf.grad.cpu().numpy()) <= 4e-3
     assert rel_err(dg.cpu().numpy(), gm.grad.cpu().numpy()) <= 1e-4        # column sums are fp32 throughout
     assert rel_err(db.cpu().numpy(), bt.grad.cpu().numpy()) <= 1e-4
-    assert rel_err(dbias.cpu().numpy(), zf.grad.sum(0).cpu().numpy()) <= 2e-3   # sums the ROUNDED dz rows
+    # the row kernel adds the UNROUNDED dz values in fp32 (csrc/ln_act.hip: s_dz += o before the store rounds them)
+    assert rel_err(dbias.cpu().numpy(), zf.grad.sum(0).cpu().numpy()) <= 1e-4
 
 
 def _net(in_w, L, layers, out_act, seed):
@@ -86,6 +87,12 @@ BF16_OUT, BF16_GRAD = 2e-2, 3e-2
 
 @pytest.mark.parametrize("L,layers", [(128, 2), (256, 2), (128, 3), (256, 3), (512, 2), (512, 3)])
 def test_fused_train_bf16_matches_fp32_autograd(L, layers):
+    """end to end against UNROUNDED fp32 autograd: the legitimate bf16 rounding of every stored row uses up most of
+    BF16_GRAD = 3e-2, which is wide enough to hide one row of M = 3000 missing from a weight gradient (1.8e-2), the eps of
+    the wrong layer or a skip gradient folded twice into a few rows, and only this one call shape runs (two gathers of
+    one table, one direct segment = skip).  tests/test_gpu_bf16_train_mirror.py holds the same route, on every branch of
+    its backward, to a float64 mirror that rounds where the route stores bf16: parameter gradients normwise to 2.56e-3,
+    bf16 rows element by element (tests/bf16_train_ref.py; its mutants show what that bar rejects)."""
     from hierarchicalgnn_amd import _lib, fused, mlp
     g = torch.Generator().manual_seed(L + layers)
     out_act = "Tanh" if layers == 2 else "GELU"
